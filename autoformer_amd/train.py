@@ -248,6 +248,7 @@ class TrainStep:
         # gradients (the real-data branch D(x) included) are complete only at the end of the
         # backward, not when the decoder hook fires, so they are stepped with the encoder slice
         owner = torch.nn.ModuleList([*extra_modules, model]) if extra_modules else model
+        self.owner = owner
         self.params, self.flat, self.gflat = D.flatten_params_(owner)
         D.broadcast_(self.flat)
         set_grad_sink(True)  # kernels accumulate straight into the flat gradient buffer
@@ -303,6 +304,28 @@ class TrainStep:
         """Raise DeviceFault if any kernel of the steps so far reported a fault (synchronises)."""
         torch.cuda.synchronize()
         K.raise_on_fault(self._fault.item())
+
+    def _state_tensors(self):
+        return [self.flat, self.opt.m, self.opt.v, self.opt.state, *self.owner.buffers()]
+
+    def state(self):
+        """Copies of everything a step reads and updates besides its inputs: the flat parameters, Adam's
+        moments and step count, and the modules' buffers (BatchNorm running statistics)."""
+        torch.cuda.synchronize()
+        return [t.detach().clone() for t in self._state_tensors()]
+
+    def set_state(self, state):
+        """Put back what state() returned, so that the next step() computes what the step after that
+        state() call computed (a recorded step included: its weight packs are rewritten from the restored
+        parameters, as the end of the previous replay would have left them)."""
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            for t, s in zip(self._state_tensors(), state):
+                t.copy_(s)
+        weights_changed()
+        if self.recorded is not None:
+            repack_in_place(self._pack_groups[0] + self._pack_groups[1], "graph_all")
+        torch.cuda.synchronize()
 
     def _decoder_done(self):
         set_tail(True)  # the rest of the backward is the encoder's full pass (layers.main_wgrad)

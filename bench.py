@@ -3,8 +3,15 @@
 bwd + Adam) on synthetic (B, T, 80) batches resident in HBM, 1..N GPUs (one process per
 GPU, data parallel, RCCL gradient all-reduce).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds the
+legs that take runs of their own: the dominant kernel's roofline (HIP events around its launches
+in the timed region + isolated replays) and the CPU-oracle baseline.  --dump-outputs DIR steps the
+timed path once more after the timed steps, from the state the first step started from, and writes
+what that step hands its caller (loss, loss terms, mel_postnet, gradient norms) as DIR/<name>.npy:
+the same arrays in every run with the same arguments.
 
 With --gpus N > 1 and no launcher environment (WORLD_SIZE unset) the script starts the N
 ranks itself: N child processes of this script with RANK / LOCAL_RANK / WORLD_SIZE /
@@ -236,6 +243,44 @@ def cpu_baseline(B, T, freq, steps=5):
                       f"{torch.get_num_threads()} intra-op threads"}
 
 
+DUMP_BYTES = 64 * 10**6     # --dump-outputs: upper bound on what one run writes
+
+
+class StepOutputs:
+    """Keeps what the step's loss block returned at its last call: (total, loss terms, mel_postnet).  A
+    recorded step rewrites those tensors in place at every replay, so they stay current."""
+
+    def __init__(self, trainer):
+        self.inner, self.last = trainer.loss_fn, None
+        trainer.loss_fn = self
+
+    def __call__(self, *args):
+        self.last = self.inner(*args)
+        return self.last
+
+
+def dump_outputs(path, loss, outs, trainer):
+    """Write what one step handed its caller as .npy files under `path`: `loss` (the total the step
+    returned), `loss_terms` (the terms of the loss block, train.py's l_id, l_id_psnt, l_cd [, l_adjust]),
+    `mel_postnet` (the model's output, B x 1 x T x 80; the leading utterances that fit DUMP_BYTES), all
+    float32, and `grad_norm` (float32 too): the L2 norm of the step's gradient, whole and per top-level
+    module of the model(s), in registration order."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    _, terms, mel = outs.last
+    mel = mel.detach().float().cpu().numpy()
+    keep = max(1, (DUMP_BYTES - (1 << 20)) // max(1, mel[0].size * 4))
+    norms = [trainer.gflat.double().norm().item()]
+    for _, child in trainer.owner.named_children():
+        g = [p.grad.double().reshape(-1) for p in child.parameters() if p.grad is not None]
+        norms.append(torch.cat(g).norm().item() if g else 0.0)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+    np.save(os.path.join(path, "loss_terms.npy"), np.array([t.item() for t in terms], np.float32))
+    np.save(os.path.join(path, "mel_postnet.npy"), mel[:keep])
+    np.save(os.path.join(path, "grad_norm.npy"), np.array(norms, np.float32))
+
+
 def launch_ranks(n):
     """Start n ranks of this script (one per GPU) and wait for them; returns the exit code.
     The parent never touches the GPU (torch.cuda.device_count() does not initialise HIP on
@@ -296,11 +341,21 @@ def main():
                          "step's kernels, streams and event edges without its Python -- the default")
     ap.add_argument("--eager", action="store_true",
                     help="step from Python every time (no recorded replay)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the dominant kernel's `roofline` (events "
+                         "around its launches in the timed region + isolated replays) and `cpu_baseline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, step the timed path once more from the initial weights and "
+                         "optimizer state and write its loss, loss terms, mel_postnet and gradient norms as "
+                         "DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip `roofline`")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    kernel_legs = args.full and not args.no_kernel_timing and args.model == "AutoVC"
     # diagnostic ablations skip work inside the step: a number measured under them is not the metric
     skipped = [k for k in ("AVC_ABLATE_WGRAD",) if os.environ.get(k, "0") not in ("", "0")]
     if skipped:
@@ -352,6 +407,8 @@ def main():
         trainer = TrainStep(model, lr=1e-4, extra=gan_extra(disc), extra_modules=[disc])
     else:
         trainer = TrainStep(model, lr=1e-4)
+    if args.dump_outputs:
+        outs, initial = StepOutputs(trainer), trainer.state()
 
     # the recorded replay (replay.py) is the default step form of the AutoVC steps: the same kernels,
     # streams and event edges as the eager step, with no per-kernel Python, so a slow host does not
@@ -371,7 +428,7 @@ def main():
     from autoformer_amd import kernels as K
 
     # dominant-kernel launches inside the timed region, timed by HIP events on their stream
-    K.LAUNCH_TIMING = [] if (not args.no_kernel_timing and args.model == "AutoVC") else None
+    K.LAUNCH_TIMING = [] if kernel_legs else None
     if world > 1:
         trainer.comm_timing = []
     t0 = time.perf_counter()
@@ -393,6 +450,19 @@ def main():
     ms = elapsed / args.steps * 1e3
     frames = world * B * T
     value = frames / (elapsed / args.steps)
+    evs, K.LAUNCH_TIMING = K.LAUNCH_TIMING or [], None
+    if args.dump_outputs:
+        # The bf16 step is not bit-reproducible (split-K sums are float atomics in arrival order, and Adam
+        # turns sign flips of noise-level gradients into whole-lr moves), and training amplifies that:
+        # after 20 steps two runs' mel_postnet differ by 16 % (relative L2), after 200 by 22 %.  So the
+        # outputs written are those of the timed path stepped once more from the state the first step
+        # started from (weights, Adam moments, BN statistics): the same in every run whatever --steps and
+        # --warmup are (loss, loss terms and mel_postnet bit for bit; the gradient norms to fp32 rounding).
+        trainer.set_state(initial)
+        loss = trainer.step(x, e)
+        trainer.check()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, loss, outs, trainer)
 
     if rank != 0:
         if world > 1:
@@ -423,8 +493,7 @@ def main():
         out["allreduce_ms"] = round(comm_ms, 4)
         out["allreduce_bytes_per_step"] = trainer.gflat.numel() * trainer.gflat.element_size()
         out["collective"] = f"{dist.get_backend()} all_reduce AVG, {D.BUCKET_BYTES >> 20} MiB buckets"
-    if not args.no_kernel_timing and args.model == "AutoVC":
-        evs, K.LAUNCH_TIMING = K.LAUNCH_TIMING or [], None
+    if kernel_legs:
         wave = wavefront_bwd(B)
         dominant = DOMINANT_WAVE if wave else DOMINANT
         # isolated replays (also: algorithmic bytes / FLOP)
@@ -448,7 +517,7 @@ def main():
                            "alg_bytes_per_launch": kt["bytes"], "hbm_achieved_gbs": round(gbs, 1),
                            "hbm_frac": round(gbs / PEAK_HBM_GBS, 5), "traffic_source": src,
                            "counters": pmc_mfma(dominant)}
-    if world == 1 and not args.no_cpu_baseline and default:
+    if args.full and world == 1 and not args.no_cpu_baseline and default:
         out["cpu_baseline"] = cpu_baseline(B, T, freq)
     print(json.dumps(out), flush=True)
     if world > 1:

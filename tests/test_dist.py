@@ -45,7 +45,9 @@ def _worker(rank, world, port, q):
         D.finish_allreduce_(early)
         D.finish_allreduce_(late)
         torch.testing.assert_close(g2, torch.arange(gflat.numel(), dtype=torch.float32) * 1.5)
-        q.put((rank, flat.clone(), gflat.clone(), m[0].weight.grad.clone()))
+        # as numpy arrays: pickled by value.  A tensor crosses the queue as a shared-memory handle the
+        # parent has to fetch from this process, which may have exited by then (connection reset)
+        q.put((rank, flat.numpy().copy(), gflat.numpy().copy(), m[0].weight.grad.numpy().copy()))
         dist.barrier()
         dist.destroy_process_group()
     except Exception as e:  # surface worker failures to the parent
@@ -65,7 +67,7 @@ def test_dp_broadcast_and_allreduce_world2():
     for _ in range(2):
         rank, flat, gflat, g0 = q.get(timeout=100)
         assert not isinstance(flat, str), flat
-        res[rank] = (flat, gflat, g0)
+        res[rank] = tuple(torch.from_numpy(a) for a in (flat, gflat, g0))
     for p in procs:
         p.join(30)
         assert p.exitcode == 0

@@ -23,10 +23,10 @@ python3 $R/tools/pmc_mfma.py $(find $OUT/mfma -name "*counter_collection.csv" | 
 cp $OUT/pmc_mfma_step.json $R/profiles/${PFX}_pmc_mfma_step.json
 timeout -k 10 120 python3 $R/tools/lstm_trace.py > $OUT/lstm_trace.txt 2>&1 || exit 1
 timeout -k 10 120 python3 $R/tools/lstm2_bwd_bench.py 10 > $OUT/lstm2_bwd_bench.txt 2>&1 || exit 1
-timeout -k 10 400 python3 $R/bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
+timeout -k 10 400 python3 $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 cat $OUT/bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- \
-    python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/prof.log 2>&1 || exit 1
+    python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/prof.log 2>&1 || exit 1
 CSV=$(find $OUT/prof -name "run_kernel_trace.csv" | head -1)
 python3 $R/tools/step_breakdown.py $CSV 30 > $OUT/step_breakdown.txt
 cp $(find $OUT/prof -name "run_kernel_stats.csv" | head -1) $OUT/kernel_stats.csv

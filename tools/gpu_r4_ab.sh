@@ -9,8 +9,8 @@ BASE=$R/autoformer_amd/libautovc_hip_base.so
 for rep in 1 2 3; do
   for v in base new; do
     if [ $v = base ]; then export AVC_LIB_PATH=$BASE; else unset AVC_LIB_PATH; fi
-    timeout -k 10 200 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/c2.$v.$rep.json 2>/dev/null || exit 1
-    timeout -k 10 200 python -u bench.py --model MetaConv --steps 10 --warmup 3 --no-cpu-baseline > $OUT/c4.$v.$rep.json 2>/dev/null || exit 1
+    timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/c2.$v.$rep.json 2>/dev/null || exit 1
+    timeout -k 10 200 python -u bench.py --full --model MetaConv --steps 10 --warmup 3 --no-cpu-baseline > $OUT/c4.$v.$rep.json 2>/dev/null || exit 1
   done
 done
 for v in base new; do
