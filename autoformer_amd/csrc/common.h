@@ -175,7 +175,7 @@ unsigned* avc_counter_slots(int n, hipStream_t s);
 // reserved ranges never overlap while fewer than `pool` slots are live (a plain
 // fetch_add(n) moved the crossing request to 0 but advanced the cursor by n only).
 unsigned avc_ring_reserve(std::atomic<unsigned>& cursor, unsigned n, unsigned pool);
-// the process fault word of the current device (avc_set_fault_word; lstm.hip), nullable
+// the process fault word of the current device (avc_set_fault_word; lstm.hip, the host state shared by the LSTM files), nullable
 unsigned* avc_fault_ptr();
 // n floats of a device pool that is all zero between uses: the user leaves its region zeroed
 // (a ring like avc_counter_slots; created on first use outside a stream capture)

@@ -54,7 +54,7 @@ class PatchEmbed(nn.Module):
 class LSTMParams(nn.Module):
     """Parameters of nn.LSTM(batch_first=True) under the same names (weight_ih_l0, ...,
     *_reverse) and with nn.LSTM's U(-1/sqrt(H), 1/sqrt(H)) initialisation.  The recurrence
-    runs in lstm.hip; ``flatten_parameters`` (a cuDNN weight-packing hint in the reference,
+    runs in csrc/lstm*.hip; ``flatten_parameters`` (a cuDNN weight-packing hint in the reference,
     AutoVC.py:54) is a no-op here."""
 
     def __init__(self, input_size, hidden_size, num_layers=1, batch_first=True, bidirectional=False):

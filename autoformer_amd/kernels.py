@@ -367,7 +367,7 @@ def lstm_timeout_flag(hbuf, B, H):
 
 
 def lstm_persistent_fwd(B, H, dirs):
-    """Whether avc_lstm_fwd takes the one-launch persistent path (asked of lstm.hip: shape,
+    """Whether avc_lstm_fwd takes the one-launch persistent path (asked of lstm_persist.hip: shape,
     compute mode and the occupancy check of the whole grid)."""
     return bool(L.lib().avc_lstm_persistent(int(B), int(H), int(dirs), _COMPUTE, 0))
 
@@ -547,7 +547,7 @@ def lstm2_bwd(dh1, c0, g0, c1, g1, wt0, wti1, wt1, B, T, H, fp32=True, db=False)
 
 
 def lstm_persistent_bwd(B, H, dirs):
-    """Whether avc_lstm_bwd takes the one-launch persistent path (asked of lstm.hip)."""
+    """Whether avc_lstm_bwd takes the one-launch persistent path (asked of lstm_persist.hip)."""
     return bool(L.lib().avc_lstm_persistent(int(B), int(H), int(dirs), _COMPUTE, 1))
 
 

@@ -317,7 +317,7 @@ int avc_lstm_set_spin(unsigned spins);
  * Same as the AVC_RING / AVC_RING_WIN environment variables.  Returns 0. */
 int avc_gemm_set_ring(int mode, int bm, int bn, int nst, int gm, int win);
 
-/* Decoder lstm2 BACKWARD, both layers in one persistent launch (layer wavefront, lstm.hip
+/* Decoder lstm2 BACKWARD, both layers in one persistent launch (layer wavefront, lstm2.hip
  * lstm2_persist_bwd): tick k runs layer 1 at step T-1-k and layer 0 at step T-k; layer 0's upstream
  * gradient dG1 W_ih1 is formed inside the recurrence.  dh1 = dL/dh of layer 1's output (B,T,H);
  * c0/gates0, c1/gates1 the forward's cell states and activated gates (avc_lstm2_fwd); w_hh0_t,

@@ -1,4 +1,4 @@
-"""The encoder BiLSTM on MFMA (lstm_mfma_fwd / lstm_mfma_bwd, csrc/lstm.hip; reference
+"""The encoder BiLSTM on MFMA (lstm_mfma_fwd / lstm_mfma_bwd, csrc/lstm_small.hip; reference
 factory/AutoVC.py:43,54-55 -- nn.LSTM(512, 44, 2, batch_first=True, bidirectional=True)) against a
 float64 PyTorch restatement of the recurrence on the same inputs.
 

@@ -1,4 +1,4 @@
-"""The decoder lstm2 backward as ONE two-layer wavefront launch (avc_lstm2_bwd, lstm.hip
+"""The decoder lstm2 backward as ONE two-layer wavefront launch (avc_lstm2_bwd, lstm2.hip
 lstm2_persist_bwd; AutoVC.py:96,110's nn.LSTM(512, 1024, 2)) against the same backward as two
 single-layer persistent launches with the dX1 = dG1 W_ih1 GEMM between them (the path it replaces),
 and the whole step's gradients with the wavefront on / off.  Both use bf16 payloads and weights with

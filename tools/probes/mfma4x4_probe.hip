@@ -1,6 +1,6 @@
 // Layout / timing probe of v_mfma_f32_4x4x4_16b_bf16 (__builtin_amdgcn_mfma_f32_4x4x4bf16_1k) on
 // gfx950: which lane / element of A and B feeds which lane / register of D, and the issue cost of a
-// dependent chain (the encoder BiLSTM's recurrent product, lstm.hip lstm_mfma_*).
+// dependent chain (the encoder BiLSTM's recurrent product, lstm_small.hip lstm_mfma_*).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
