@@ -150,13 +150,20 @@ __global__ void conv_pack_kernel(const float* w, void* out, int dtype, int Co, i
 // Weight-pack units, LDS-staged where the layout changes, 256 threads (round 6: the per-element forms
 // scattered 2-B stores Ci or K*Co elements apart -- ~64 B of memory traffic per stored bf16 -- and the
 // batched repack ran at ~1 TB/s, 225 us beside the encoder backward for the decoder's weights).  Every
-// unit keeps 16 independent loads per thread in flight and needs at most PK_BUF floats of LDS (17 KiB,
-// so a pack workgroup still fits beside a conv ring workgroup).  W[co][ci][k] fp32 ->
+// unit keeps 16 independent loads per thread in flight and needs at most PK_BUF floats of LDS
+// (max(64*65, 16*8*33) = 4224 floats = 16.5 KiB, under the 17 KiB at which a pack workgroup still fits
+// beside a conv ring workgroup).  W[co][ci][k] fp32 ->
 //   mode 0, Wf[co][k][ci]:     unit = 4 output x 64 input channels (K <= 16; 4 runs of 64*K floats in,
 //                              4*K runs of 64 out);
 //   mode 1, Wd[ci][K-1-k][co]: unit = 32 output x 16 input channels (K <= 8; 32 runs of 16*K floats in,
 //                              16*K runs of 32 out).
-constexpr int PK_KMAX_F = 16, PK_KMAX_D = 8, PK_BUF = 64 * 65;
+constexpr int PK_KMAX_F = 16, PK_KMAX_D = 8;
+constexpr int PK_BUF = 64 * 65 > 16 * PK_KMAX_D * 33 ? 64 * 65 : 16 * PK_KMAX_D * 33;
+// highest LDS index of each unit at its K limit: mode 0 writes buf[(r*K + k)*65 + cil] with r < 4, k < K,
+// cil < 64; mode 1 writes buf[rem*33 + r] with rem < 16*K, r < 32.
+static_assert((3 * PK_KMAX_F + PK_KMAX_F - 1) * 65 + 63 < PK_BUF, "mode-0 pack unit overruns PK_BUF");
+static_assert((16 * PK_KMAX_D - 1) * 33 + 31 < PK_BUF, "mode-1 pack unit overruns PK_BUF");
+static_assert(PK_BUF * sizeof(float) <= 17 * 1024, "pack unit LDS exceeds its 17 KiB budget");
 __host__ __device__ constexpr long long conv_pack_units(int Co, int Ci, int mode) {
   return mode == 0 ? (long long)((Co + 3) / 4) * ((Ci + 63) / 64) : (long long)((Co + 31) / 32) * ((Ci + 15) / 16);
 }

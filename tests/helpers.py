@@ -9,6 +9,63 @@ def rel_inf(a, b):
     return np.abs(a - b).max() / max(np.abs(b).max(), 1e-30)
 
 
+def _bf16_round(x):
+    return x.bfloat16().double()
+
+
+def ref_fwd(xp, w, B, T, H, dirs, round_rec=False):
+    """The LSTM recurrence (h0 = c0 = 0, direction 1 in reversed time) in float64.
+    xp (B, T, dirs*4H), w (dirs*4H, H): h, c, activated gates, all (B, T, dirs*.) float64.
+    round_rec rounds h_{t-1} to bf16 before the recurrent product, as the bf16 large-H kernels do."""
+    G = 4 * H
+    h = torch.zeros(B, T, dirs * H, dtype=torch.float64)
+    c = torch.zeros_like(h)
+    g = torch.zeros(B, T, dirs * G, dtype=torch.float64)
+    for d in range(dirs):
+        W = w[d * G:(d + 1) * G]
+        hp = torch.zeros(B, H, dtype=torch.float64)
+        cp = torch.zeros_like(hp)
+        for s in range(T):
+            t = T - 1 - s if d else s
+            pre = xp[:, t, d * G:(d + 1) * G] + (_bf16_round(hp) if round_rec else hp) @ W.t()
+            i, f, gg, o = torch.sigmoid(pre[:, :H]), torch.sigmoid(pre[:, H:2 * H]), torch.tanh(
+                pre[:, 2 * H:3 * H]), torch.sigmoid(pre[:, 3 * H:])
+            cp = f * cp + i * gg
+            hp = o * torch.tanh(cp)
+            h[:, t, d * H:(d + 1) * H] = hp
+            c[:, t, d * H:(d + 1) * H] = cp
+            g[:, t, d * G:(d + 1) * G] = torch.cat([i, f, gg, o], 1)
+    return h, c, g
+
+
+def ref_bwd(dh_out, c, g, w, B, T, H, dirs, round_rec=False, c0=None):
+    """dL/d(pre-activation gates) (B, T, dirs*4H) float64 from the forward's c and activated gates.
+    round_rec rounds the previous backward step's dG to bf16 before the recurrent product; c0 (B, dirs*H)
+    is the cell state before each direction's first step (default: zeros, as the kernels have it)."""
+    G = 4 * H
+    dg = torch.zeros(B, T, dirs * G, dtype=torch.float64)
+    for d in range(dirs):
+        W = w[d * G:(d + 1) * G]
+        dgn = torch.zeros(B, G, dtype=torch.float64)
+        dc = torch.zeros(B, H, dtype=torch.float64)
+        for s in range(T):
+            t = s if d else T - 1 - s  # opposite to the forward
+            tp = t + 1 if d else t - 1
+            gt = g[:, t, d * G:(d + 1) * G]
+            i, f, gg, o = gt[:, :H], gt[:, H:2 * H], gt[:, 2 * H:3 * H], gt[:, 3 * H:]
+            ct = c[:, t, d * H:(d + 1) * H]
+            c_first = torch.zeros_like(ct) if c0 is None else c0[:, d * H:(d + 1) * H]
+            cp = c[:, tp, d * H:(d + 1) * H] if 0 <= tp < T else c_first
+            dh = dh_out[:, t, d * H:(d + 1) * H] + (_bf16_round(dgn) if round_rec else dgn) @ W
+            tc = torch.tanh(ct)
+            dcs = dc + dh * o * (1 - tc * tc)
+            dgn = torch.cat([dcs * gg * i * (1 - i), dcs * cp * f * (1 - f), dcs * i * (1 - gg * gg),
+                             dh * tc * o * (1 - o)], 1)
+            dc = dcs * f
+            dg[:, t, d * G:(d + 1) * G] = dgn
+    return dg
+
+
 def grad_mismatches(model, g, tol=1e-2, head_tol=1e-2,
                     bn_fed_bias=lambda n: "conv.bias" in n and "postnet.convolutions.4" not in n):
     """Per-parameter check against the golden gradient norm (rel <= tol) and first-64-element

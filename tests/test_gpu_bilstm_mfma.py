@@ -10,6 +10,8 @@ are covered."""
 import pytest
 import torch
 
+from .helpers import ref_bwd, ref_fwd
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -19,54 +21,6 @@ def relf(a, b):
     a = a.double().cpu()
     b = b.double().cpu()
     return float((a - b).norm() / max(b.norm().item(), 1e-30))
-
-
-def ref_fwd(xp, w, B, T, H, dirs):
-    """xp (B, T, dirs*4H), w (dirs*4H, H): h, c, activated gates, all (B, T, dirs*.) float64."""
-    G = 4 * H
-    h = torch.zeros(B, T, dirs * H, dtype=torch.float64)
-    c = torch.zeros_like(h)
-    g = torch.zeros(B, T, dirs * G, dtype=torch.float64)
-    for d in range(dirs):
-        W = w[d * G:(d + 1) * G]
-        hp = torch.zeros(B, H, dtype=torch.float64)
-        cp = torch.zeros_like(hp)
-        for s in range(T):
-            t = T - 1 - s if d else s
-            pre = xp[:, t, d * G:(d + 1) * G] + hp @ W.t()
-            i, f, gg, o = torch.sigmoid(pre[:, :H]), torch.sigmoid(pre[:, H:2 * H]), torch.tanh(
-                pre[:, 2 * H:3 * H]), torch.sigmoid(pre[:, 3 * H:])
-            cp = f * cp + i * gg
-            hp = o * torch.tanh(cp)
-            h[:, t, d * H:(d + 1) * H] = hp
-            c[:, t, d * H:(d + 1) * H] = cp
-            g[:, t, d * G:(d + 1) * G] = torch.cat([i, f, gg, o], 1)
-    return h, c, g
-
-
-def ref_bwd(dh_out, c, g, w, B, T, H, dirs):
-    """dL/d(pre-activation gates) (B, T, dirs*4H) float64 from the forward's c and activated gates."""
-    G = 4 * H
-    dg = torch.zeros(B, T, dirs * G, dtype=torch.float64)
-    for d in range(dirs):
-        W = w[d * G:(d + 1) * G]
-        dgn = torch.zeros(B, G, dtype=torch.float64)
-        dc = torch.zeros(B, H, dtype=torch.float64)
-        for s in range(T):
-            t = s if d else T - 1 - s  # opposite to the forward
-            tp = t + 1 if d else t - 1
-            gt = g[:, t, d * G:(d + 1) * G]
-            i, f, gg, o = gt[:, :H], gt[:, H:2 * H], gt[:, 2 * H:3 * H], gt[:, 3 * H:]
-            ct = c[:, t, d * H:(d + 1) * H]
-            cp = c[:, tp, d * H:(d + 1) * H] if 0 <= tp < T else torch.zeros_like(ct)
-            dh = dh_out[:, t, d * H:(d + 1) * H] + dgn @ W
-            tc = torch.tanh(ct)
-            dcs = dc + dh * o * (1 - tc * tc)
-            dgn = torch.cat([dcs * gg * i * (1 - i), dcs * cp * f * (1 - f), dcs * i * (1 - gg * gg),
-                             dh * tc * o * (1 - o)], 1)
-            dc = dcs * f
-            dg[:, t, d * G:(d + 1) * G] = dgn
-    return dg
 
 
 @pytest.mark.parametrize("B,T,H,dirs", [(64, 128, 44, 2), (3, 33, 44, 2), (7, 20, 44, 1), (5, 17, 16, 1),

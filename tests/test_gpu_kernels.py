@@ -337,8 +337,11 @@ def test_lstm_layer_fp32(B, T, In, H, dirs):
     assert not bad, bad
 
 
-@pytest.mark.parametrize("B,T,In,H,dirs", [(4, 33, 512, 44, 2), (20, 16, 512, 1024, 1), (64, 8, 344, 512, 1)])
+@pytest.mark.parametrize("B,T,In,H,dirs", [(4, 33, 512, 44, 2), (20, 16, 512, 1024, 1), (64, 8, 344, 512, 1),
+                                           (3, 9, 96, 128, 2), (72, 4, 64, 1024, 1)])
 def test_lstm_layer_bf16(B, T, In, H, dirs):
+    """The last two shapes take the per-step recurrences (bidirectional at H > 64; a batch whose
+    persistent grid does not fit): the weight-gradient GEMMs then run from a dG without a bf16 twin."""
     res = _lstm_case(B, T, In, H, dirs, "bf16")
     bad = {k: v for k, v in res.items() if v > 3e-2}
     assert not bad, bad
@@ -690,10 +693,13 @@ def test_gemm_tt_time_shift_window():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("Co,Ci,Kw", [(512, 512, 5), (96, 40, 5), (80, 512, 5), (512, 80, 5), (33, 65, 3), (24, 44, 9)])
+@pytest.mark.parametrize("Co,Ci,Kw", [(512, 512, 5), (96, 40, 5), (80, 512, 5), (512, 80, 5), (33, 65, 3), (24, 44, 9),
+                                      (40, 24, 8), (33, 17, 8), (64, 16, 7), (8, 70, 16), (5, 65, 17)])
 def test_conv_pack_matches_permute(Co, Ci, Kw):
-    """avc_conv_pack (LDS-staged tiles for <= 8 taps, the per-element kernel above) against the torch
-    permutations it stands for: Wf[co][k][ci] and the flipped Wd[ci][K-1-k][co], bf16 and fp32."""
+    """avc_conv_pack (LDS-staged tiles for <= 16 taps in mode 0 and <= 8 in mode 1, the per-element kernel
+    above) against the torch permutations it stands for: Wf[co][k][ci] and the flipped Wd[ci][K-1-k][co],
+    bf16 and fp32.  K = 8 and K = 16 are the tile limits of mode 1 / mode 0 (ragged Co / Ci tails), K = 7
+    sits just inside, K = 17 takes the per-element form in both modes."""
     from autoformer_amd import kernels as Kr
 
     w = torch.randn(Co, Ci, Kw, device=DEV)
@@ -706,18 +712,41 @@ def test_conv_pack_matches_permute(Co, Ci, Kw):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("Co,Ci,Kw", [(40, 24, 8), (33, 17, 8), (8, 70, 16)])
+def test_conv_pack_writes_inside_its_output(Co, Ci, Kw):
+    """avc_conv_pack at the tile limits (K = 8 for mode 1, K = 16 for mode 0) into a view of a larger
+    tensor: the 64 sentinel elements on each side of the view stay untouched, and the view holds the pack."""
+    from autoformer_amd import kernels as Kr
+
+    w = torch.randn(Co, Ci, Kw, device=DEV)
+    n, pad, sentinel = Co * Ci * Kw, 64, -12288.0  # exact in bf16
+    for dt, tdt in ((Kr.BF16, torch.bfloat16), (Kr.F32, torch.float32)):
+        for mode in (0, 1):
+            big = torch.full((n + 2 * pad,), sentinel, device=DEV, dtype=tdt)
+            out = big[pad:pad + n]
+            Kr.L.call("avc_conv_pack", w.data_ptr(), out.data_ptr(), dt, Co, Ci, Kw, mode, Kr.stream())
+            torch.cuda.synchronize()
+            assert bool((big[:pad] == sentinel).all()) and bool((big[pad + n:] == sentinel).all()), (dt, mode)
+            ref = w.permute(0, 2, 1) if mode == 0 else w.flip(2).permute(1, 2, 0)
+            assert torch.equal(out, ref.to(tdt).reshape(-1)), (dt, mode)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Kw", [5, 8])
 @pytest.mark.parametrize("Co,Ci,G,In,H", [(96, 40, 176, 72, 44), (512, 512, 4096, 1024, 1024), (33, 70, 130, 67, 33)])
-def test_pack_batch_matches_individual_packs(Co, Ci, G, In, H):
-    """avc_pack_batch (one launch for many packs) == the per-pack kernels it replaces, on ragged shapes too
-    (tails of the 64 x 64 transpose tiles, the 4096-element copy units and the conv tiles; odd sizes take
-    the unaligned scalar forms), the conv0 fold's channel-slice packs in all four layouts included."""
+def test_pack_batch_matches_individual_packs(Co, Ci, G, In, H, Kw):
+    """avc_pack_batch (one launch for many packs) == the per-pack kernels it replaces and the plain torch
+    expressions they stand for, on ragged shapes too (tails of the 64 x 64 transpose tiles, the 4096-element
+    copy units and the conv tiles; odd sizes take the unaligned scalar forms), the conv0 fold's channel-slice
+    packs in all four layouts included.  Kw = 8 is the tap limit of the CONV_D tile, whose staging buffer
+    sits in front of the kernel's op tables in LDS: the ops after it would be misdirected by an overrun."""
     import autoformer_amd as A
     from autoformer_amd import kernels as Kr
     from autoformer_amd import layers as Lyr
 
     A.set_compute("bf16")
     dev = "cuda:0"
-    w = torch.randn(Co, Ci, 5, device=dev)
+    w = torch.randn(Co, Ci, Kw, device=dev)
     wih, whh = torch.randn(G, In, device=dev), torch.randn(G, H, device=dev)
     bih, bhh = torch.randn(G, device=dev), torch.randn(G, device=dev)
     # the conv0 fold's channel slices (avc_conv_pack_slice modes 0-3: padded, flipped, per tap, padded Co)
@@ -728,26 +757,31 @@ def test_pack_batch_matches_individual_packs(Co, Ci, G, In, H):
     ref += [Kr.conv_pack_slice(w, *sl, Kr.BF16) for sl in slices]
     outs = [torch.empty_like(t) for t in ref]
     from autoformer_amd._lib import PACK_ADD, PACK_CONV_D, PACK_CONV_F, PACK_CONV_SLICE, PACK_COPY, PACK_TRANSPOSE
-    ops = [{"src": w.data_ptr(), "dst": outs[0].data_ptr(), "kind": PACK_CONV_F, "dtype": Kr.BF16, "dims": (Co, Ci, 5)},
-           {"src": w.data_ptr(), "dst": outs[1].data_ptr(), "kind": PACK_CONV_D, "dtype": Kr.BF16, "dims": (Co, Ci, 5)},
+    ops = [{"src": w.data_ptr(), "dst": outs[0].data_ptr(), "kind": PACK_CONV_F, "dtype": Kr.BF16, "dims": (Co, Ci, Kw)},
+           {"src": w.data_ptr(), "dst": outs[1].data_ptr(), "kind": PACK_CONV_D, "dtype": Kr.BF16, "dims": (Co, Ci, Kw)},
            {"src": wih.data_ptr(), "dst": outs[2].data_ptr(), "kind": PACK_COPY, "dtype": Kr.BF16, "dims": (G * In,)},
            {"src": whh.data_ptr(), "dst": outs[3].data_ptr(), "kind": PACK_TRANSPOSE, "dtype": Kr.BF16,
             "dims": (G, H), "ld": G},
            {"src": bih.data_ptr(), "src2": bhh.data_ptr(), "dst": outs[4].data_ptr(), "kind": PACK_ADD,
             "dtype": Kr.F32, "dims": (G,)}]
-    ops += [{"src": w.data_ptr(), "dst": o.data_ptr(), "kind": PACK_CONV_SLICE, "dtype": Kr.BF16, "dims": (Co, Ci, 5),
+    ops += [{"src": w.data_ptr(), "dst": o.data_ptr(), "kind": PACK_CONV_SLICE, "dtype": Kr.BF16, "dims": (Co, Ci, Kw),
              "slice": sl} for o, sl in zip(outs[5:], slices)]
 
     class _C:  # the PackCache surface _batch_plan reads
         pass
     c = _C()
     c.params, c.val, c.ops = [w, wih, whh, bih, bhh], tuple(outs), lambda val: ops
+    Lyr._BATCH.pop(99, None)  # plans are cached by buffer address, which a later case may meet again
     plan = Lyr._batch_plan([c], group=99)
     Kr.L.call("avc_pack_batch", plan["ops"].data_ptr(), plan["prefix"].data_ptr(), plan["n"], plan["total"],
               Kr.stream())
     torch.cuda.synchronize()
     for a, b in zip(outs, ref):
         assert torch.equal(a, b)
+    plain = [w.permute(0, 2, 1).bfloat16().reshape(Co, Kw * Ci),
+             w.flip(2).permute(1, 2, 0).bfloat16().reshape(Ci, Kw * Co), wih.bfloat16(), whh.t().bfloat16(), bih + bhh]
+    for i, (a, b) in enumerate(zip(outs, plain)):
+        assert torch.equal(a, b), i
 
 
 @pytest.mark.parametrize("B", [64, 20])
