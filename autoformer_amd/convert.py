@@ -35,11 +35,12 @@ def crop_mel(mel: np.ndarray, len_crop: int, rng=np.random):
 class Converter:
     """convert(mel_source, emb_org, emb_trg) -> converted mel (T', 80) on the host."""
 
-    def __init__(self, model, len_crop: int, device="cuda:0", vocoder=None):
+    def __init__(self, model, len_crop: int, device="cuda:0", vocoder=None, embedder=None):
         self.model = model
         self.len_crop = len_crop
         self.device = torch.device(device)
         self.vocoder = vocoder  # autoformer_amd.melgan.MelVocoder (evaluate.py:24) or None
+        self.embedder = embedder  # factory.LstmDV.LstmDV (evaluate.py:25) or None: convert_between
 
     @torch.no_grad()
     def get_wavs(self, mel, frames: bool = False):
@@ -94,3 +95,16 @@ class Converter:
         _, _, mel_trans = self.get_trans_mel(mel_source, mel_target, emb_org, emb_trg, isAdjust, isAdain,
                                              isPlay=trim)
         return mel_trans[0].float().cpu().numpy()
+
+    @torch.no_grad()
+    def convert_between(self, mel_source: np.ndarray, src_mels, trg_mels, trim: bool = True, **kw):
+        """Conversion between two speakers given only recordings of them: the d-vectors of src_mels and
+        trg_mels (lists of (T, 80) mels; autoformer_amd.embed.speaker_dvector, evaluate.py:100-106) are
+        emb_org / emb_trg of convert()."""
+        if self.embedder is None:
+            raise RuntimeError("Converter was built without an embedder (pass embedder=LstmDV(...))")
+        from .embed import speaker_dvector
+
+        e_org = speaker_dvector(self.embedder, src_mels, self.len_crop)
+        e_trg = speaker_dvector(self.embedder, trg_mels, self.len_crop)
+        return self.convert(mel_source, e_org, e_trg, trim=trim, **kw)

@@ -1,4 +1,4 @@
-// lstm_internal.h — what lstm.hip, lstm_small.hip, lstm_persist.hip and lstm2.hip share (internal
+// lstm_internal.h — what lstm.hip, lstm_small.hip, lstm_persist.hip, lstm_infer.hip and lstm2.hip share (internal
 // to libautovc_hip.so): the device helpers of the recurrences, the inter-workgroup hand-off
 // protocol of the persistent kernels, and the host state / entry points that cross files.
 #pragma once
@@ -154,8 +154,9 @@ __device__ __forceinline__ void raise_flag(unsigned* flags, int r, unsigned tag)
 
 // Every thread of the NT-thread workgroup: copy the group's `rows` payload rows of W bf16
 // (parity slot row0) into the LDS tile (row stride ap), 16-B sc1 loads, NCH chunks per
-// thread, all in flight together.
-template <int W, int NCH, int NT>
+// thread, all in flight together.  RG = rows of the LDS tile that a group may fill (PRG; the
+// forward-only recurrence of lstm_infer.hip also runs 16-row groups).
+template <int W, int NCH, int NT, int RG = PRG>
 __device__ __forceinline__ void load_group(__amdgpu_buffer_rsrc_t pay, int row0, int rows, bf16* lds, int ap) {
   constexpr int CPR = W / 8;
   const int tid = threadIdx.x;
@@ -170,7 +171,7 @@ __device__ __forceinline__ void load_group(__amdgpu_buffer_rsrc_t pay, int row0,
   for (int i = 0; i < NCH; ++i) {
     const int ch = tid + NT * i, row = ch / CPR, col = ch - row * CPR;
     // NCH is rounded up when NT does not divide the tile (H = 768): skip the overhang
-    if (NCH * NT == PRG * CPR || row < PRG) *reinterpret_cast<u32x4_t*>(lds + row * ap + col * 8) = v[i];
+    if (NCH * NT == RG * CPR || row < RG) *reinterpret_cast<u32x4_t*>(lds + row * ap + col * 8) = v[i];
   }
 }
 

@@ -8,6 +8,7 @@
 //     broadcast concats when the embedding itself is trained (AutoVC_Adjust.py:178-189)
 //   * one time step of a frame-major sequence (nn.LSTM output [:, -1, :], Adjust.py:39)
 //   * row L2 normalisation  embeds / ||embeds||         factory/Adjust.py:40-42
+//   * the d-vector head     normalize(h W^T + b)        factory/LstmDV.py:22-24 (inference)
 //
 // Everything here is HBM-bound elementwise or reduction work over (B*T, 80) mel-sized
 // tensors (2.6 MB at B=64, T=128): grid-stride float4 loads, fp64 partial sums (a
@@ -399,4 +400,69 @@ extern "C" int avc_gelu_twin(const float* g, const float* x, float* y, void* y16
   gelu_twin_kernel<<<blocks_for(n, 4 * 256), 256, 0, (hipStream_t)stream>>>(g, x, y, reinterpret_cast<bf16*>(y16), n,
                                                                              bwd);
   return avc_check_launch("avc_gelu_twin");
+}
+
+// The d-vector head of the inference path (LstmDV.py:22-24): out[b] = y / ||y||_2 with
+// y = h_last[b] W^T + bias, fp32 throughout.  One workgroup of 16 waves per utterance: h_last[b] is
+// staged in LDS, each wave takes DV_U outputs at a time -- DV_U rows of W, a float4 per lane and
+// row, all loads of a pass independent and in flight together (one output at a time left the wave
+// waiting on a load per output: 99 us at B = 64, profiles/dvec_infer_ab.txt) -- and reduces them
+// across its lanes;
+// then the workgroup reduces ||y||^2 and divides.  Replaces step-select + GEMM + row-norm there.
+constexpr int DV_THREADS = 1024, DV_U = 8;
+
+__global__ void __launch_bounds__(DV_THREADS) dvec_head_kernel(const float* __restrict__ h_last,
+                                                               const float* __restrict__ w,
+                                                               const float* __restrict__ bias, int H, int E,
+                                                               float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float dsm[];
+  float* hs = dsm;      // [H]
+  float* ys = dsm + H;  // [E]
+  __shared__ float red[DV_THREADS / 64];
+  constexpr int NW = DV_THREADS / 64;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, H4 = H >> 2;
+  const f32x4* hs4 = reinterpret_cast<const f32x4*>(hs);
+  const f32x4* w4 = reinterpret_cast<const f32x4*>(w);
+  for (int i = tid; i < H4; i += DV_THREADS)
+    reinterpret_cast<f32x4*>(hs)[i] = reinterpret_cast<const f32x4*>(h_last + (long long)b * H)[i];
+  __syncthreads();
+  for (int e0 = wv * DV_U; e0 < E; e0 += NW * DV_U) {
+    float acc[DV_U];
+#pragma unroll
+    for (int u = 0; u < DV_U; ++u) acc[u] = 0.f;
+    for (int k = lane; k < H4; k += 64) {
+      const f32x4 x = hs4[k];
+#pragma unroll
+      for (int u = 0; u < DV_U; ++u) {
+        const f32x4 a = w4[(long long)min(e0 + u, E - 1) * H4 + k];  // rows past E repeat the last one
+        acc[u] += a[0] * x[0] + a[1] * x[1] + a[2] * x[2] + a[3] * x[3];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < DV_U; ++u) {
+      float v = acc[u];
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      if (lane == 0 && e0 + u < E) ys[e0 + u] = v + (bias ? bias[e0 + u] : 0.f);
+    }
+  }
+  __syncthreads();
+  float ss = 0.f;
+  for (int e = tid; e < E; e += DV_THREADS) ss += ys[e] * ys[e];
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  if (lane == 0) red[wv] = ss;
+  __syncthreads();
+  float tot = 0.f;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) tot += red[i];
+  const float nrm = sqrtf(tot);
+  for (int e = tid; e < E; e += DV_THREADS) out[(long long)b * E + e] = ys[e] / nrm;
+}
+
+extern "C" int avc_dvec_head(const float* h_last, const float* w, const float* bias, int B, int H, int E, float* out,
+                             void* stream) {
+  AVC_CHECK_ARG(h_last && w && out && B > 0 && H > 0 && E > 0 && H % 4 == 0 && (size_t)(H + E) * 4 <= 48 * 1024,
+                "avc_dvec_head: bad shape B=%d H=%d E=%d (H a multiple of 4, (H + E) floats of LDS)", B, H, E);
+  AVC_CHECK_ARG((((uintptr_t)h_last | (uintptr_t)w) & 15) == 0, "avc_dvec_head: h_last, w must be 16-byte aligned");
+  dvec_head_kernel<<<B, DV_THREADS, (size_t)(H + E) * 4, (hipStream_t)stream>>>(h_last, w, bias, H, E, out);
+  return avc_check_launch("avc_dvec_head");
 }

@@ -482,6 +482,59 @@ def lstm_fwd(xproj, w_hh, B, T, H, dirs, hbuf=None):
     return attach_twin(h, h16), c, g
 
 
+def lstm_infer_persistent(B, H, rows=0):
+    """Whether avc_lstm_infer (the forward-only persistent recurrence) admits this shape: bf16 compute,
+    H = 768, and the whole grid of ceil(B/rows) * H/32 workgroups resident.  rows 0 = the default."""
+    return _COMPUTE == BF16 and bool(L.lib().avc_lstm_infer_persistent(int(B), int(H), int(rows)))
+
+
+def lstm_infer_scratch(B, H, device, rows=0):
+    n = int(L.lib().avc_lstm_infer_scratch_bytes(int(B), int(H), int(rows)))
+    return torch.zeros((n + 1) // 2, device=device, dtype=torch.bfloat16)
+
+
+def lstm_infer(xproj, w_hh, B, T, H, lens=None, rows=0, want_h16=True, want_last=False, hbuf=None):
+    """One layer's recurrence without anything kept for a backward (avc_lstm_infer): returns
+    (h16, h_last) -- the bf16 h of every frame (B*T, H) when want_h16, and the fp32 h of step lens[b] - 1
+    (B, H) when want_last (lens: host integers in 1..T, None = all T).  A spin timeout shows as
+    lstm_timeout_flag(hbuf) and in the fault word at the caller's next check_faults(), as for lstm_fwd."""
+    _dev(xproj, w_hh)
+    if not (want_h16 or want_last):
+        raise ValueError("lstm_infer: nothing to compute (want_h16 and want_last are both off)")
+    if w_hh.dtype != torch.bfloat16 or tuple(w_hh.shape) != (4 * H, H) or xproj.numel() != B * T * 4 * H:
+        raise ValueError("lstm_infer: xproj (B*T, 4H) fp32 and W_hh (4H, H) bf16 expected")
+    larr = None
+    if lens is not None:
+        lens = [int(v) for v in lens]
+        if len(lens) != B or min(lens) < 1 or max(lens) > T:
+            raise ValueError(f"lstm_infer: lens must hold B={B} values in 1..T={T}, got {lens}")
+        larr = (L.c_int * B)(*lens)
+    if not lstm_infer_persistent(B, H, rows):
+        raise RuntimeError(f"lstm_infer: B={B} H={H} rows={rows} is not on the persistent path "
+                           "(lstm_infer_persistent); run the layer with lstm_fwd")
+    _assert_no_collective("avc_lstm_infer")
+    dev = xproj.device
+    fault_word(dev)
+    if hbuf is None:
+        hbuf = lstm_infer_scratch(B, H, dev, rows)
+    h16 = torch.empty(B * T, H, device=dev, dtype=torch.bfloat16) if want_h16 else None
+    last = torch.empty(B, H, device=dev) if want_last else None
+    L.call("avc_lstm_infer", xproj.data_ptr(), w_hh.data_ptr(), larr, B, T, H, int(rows), _ptr(h16), _ptr(last),
+           hbuf.data_ptr(), stream())
+    return h16, last
+
+
+def dvec_head(h_last, w, bias):
+    """normalize(h_last W^T + bias) per row, fp32 (avc_dvec_head): (B, H), (E, H), (E,) -> (B, E)."""
+    _dev(h_last, w, bias)
+    B, H = h_last.shape
+    E = w.shape[0]
+    assert h_last.dtype == w.dtype == torch.float32 and w.shape[1] == H and h_last.is_contiguous() and w.is_contiguous()
+    out = torch.empty(B, E, device=h_last.device)
+    L.call("avc_dvec_head", h_last.data_ptr(), w.data_ptr(), _ptr(bias), B, H, E, out.data_ptr(), stream())
+    return out
+
+
 def lstm2_persistent(B, H, in1):
     """Whether avc_lstm2_fwd (two stacked layers, one wavefront launch) applies to this shape."""
     return bool(L.lib().avc_lstm2_persistent(int(B), int(H), int(in1), _COMPUTE))

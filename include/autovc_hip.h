@@ -346,6 +346,24 @@ int avc_gemm_ring_last(void);
  * {512, 768, 1024}, and the occupancy API admits the whole grid (ceil(B/8) * H/32
  * workgroups of 512 threads) resident at once.  0 otherwise (per-step kernels). */
 int avc_lstm_persistent(int B, int H, int dirs, int compute, int backward);
+/* Forward-only persistent recurrence for embedding extraction (no ABI bump: new symbols only).
+ * Replaces the time loop of nn.LSTM in LstmDV.py:21 under torch.no_grad(): one layer, dirs == 1,
+ * bf16 W_hh (4H, H), xproj (B, T, 4H) fp32 as avc_lstm_fwd.  Same per-step arithmetic and hand-off
+ * as avc_lstm_fwd's persistent path, but the only per-frame output is h_bf16 (B, T, H), the next
+ * layer's GEMM operand (nullable), and h_last (B, H) fp32 (nullable; not both null) receives h at
+ * step lens[b] - 1.  lens is a HOST array of B lengths, each checked to lie in 1..T before any
+ * launch (null: every length is T); rows of a padded batch run on past their own length, which
+ * cannot change what was captured.  rows = utterances per workgroup group: 8 or 16 (16: every row
+ * of the 16-row MFMA tile is an utterance, twice the utterances per launch), 0 = the measured
+ * default for B.  hbuf: avc_lstm_infer_scratch_bytes(B, H, rows) bytes, 16-byte aligned; timeout
+ * flag = u32 at byte 0, fault word and spin bound as avc_lstm_fwd.
+ * avc_lstm_infer_persistent: 1 when the shape is admitted (H = 768, B <= 512, the whole grid of
+ * ceil(B/rows) * H/32 workgroups resident at once); avc_lstm_infer refuses every other shape. */
+int avc_lstm_infer_persistent(int B, int H, int rows);
+size_t avc_lstm_infer_scratch_bytes(int B, int H, int rows);
+int avc_lstm_infer(const float* xproj, const void* w_hh, const int* lens, int B, int T, int H, int rows,
+                   void* h_bf16, float* h_last, void* hbuf, void* stream);
+
 /* 1 when avc_lstm_fwd / avc_lstm_bwd run this small-H shape (H <= 64) on the MFMA BiLSTM kernels
  * (lstm_mfma_fwd / _bwd: bf16 compute, H in {16, 32, 44, 48, 64}; ABI 29), 0 when on the packed-FMA
  * kernels.  avc_lstm_set_small_mfma: 1 selects the MFMA form, 0 the packed-FMA form (the default:
@@ -561,6 +579,11 @@ int avc_step_select(const float* src, float* dst, int B, int T, int t, int C, in
 /* Row L2 normalisation (Adjust.py:40-42) and its backward dx = (dy - y (y.dy)) / norm. */
 int avc_rownorm_fwd(const float* x, int R, int C, float* y, float* norms, void* stream);
 int avc_rownorm_bwd(const float* dy, const float* y, const float* norms, int R, int C, float* dx, void* stream);
+/* The d-vector head on the inference path (LstmDV.py:22-24): out[b] = y / ||y||_2 with
+ * y = h_last[b] W^T + bias; h_last (B, H), w (E, H), bias (E, nullable), out (B, E), fp32 throughout,
+ * one workgroup per utterance.  H a multiple of 4, (H + E) * 4 bytes <= 48 KB. */
+int avc_dvec_head(const float* h_last, const float* w, const float* bias, int B, int H, int E, float* out,
+                  void* stream);
 /* dst (R x Cd, dtype) = the first min(C, Cd) columns of src (rows lds apart), zero-filled to
  * Cd: pads the MLP-Mixer output convolution's NP channels (1849 / 121 patches) to a multiple
  * of 8 for the bf16 LDS-DMA kernels (MLPMixer.py:88-90) and crops its gradients back. */
