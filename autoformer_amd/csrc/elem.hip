@@ -818,6 +818,7 @@ extern "C" int avc_adam(float* p, const float* g, float* m, float* v, long long 
 
 extern "C" int avc_act_fwd(const float* x, float* y, long long n, int act, void* stream) {
   AVC_CHECK_ARG(x && y, "avc_act_fwd: null");
+  AVC_CHECK_ARG(act >= AVC_ACT_NONE && act <= AVC_ACT_SIGMOID, "avc_act_fwd: unknown activation code %d", act);
   if (n == 0) return 0;
   act_fwd_kernel<<<GRID1(n)>>>(x, y, n, act);
   return avc_check_launch("avc_act_fwd");
@@ -825,6 +826,9 @@ extern "C" int avc_act_fwd(const float* x, float* y, long long n, int act, void*
 
 extern "C" int avc_act_bwd(const float* g, const float* yout, float* dx, long long n, int act, void* stream) {
   AVC_CHECK_ARG(g && yout && dx, "avc_act_bwd: null");
+  // GELU has no derivative from its output (avc_gelu_bwd takes the input); act_bwd_from_out would pass g through
+  AVC_CHECK_ARG(act >= AVC_ACT_NONE && act <= AVC_ACT_SIGMOID && act != AVC_ACT_GELU,
+                "avc_act_bwd: activation code %d has no derivative from its output", act);
   if (n == 0) return 0;
   act_bwd_kernel<<<GRID1(n)>>>(g, yout, dx, n, act);
   return avc_check_launch("avc_act_bwd");

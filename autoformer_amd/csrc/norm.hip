@@ -653,11 +653,23 @@ extern "C" int avc_group_norm_bwd(const float* dy, const float* x, const float* 
   float* wsamp = ws + (size_t)nrb * C * 2;
   const long long total = (long long)B * S;
   const int ns = gn_splits(B, S);
-  if (C % 4 == 0 && a16(dy) && a16(x) && a16(dx) && a16(gamma)) {
-    float* part = wsamp + 2 * B;  // avc_norm_ws leaves room: nrb*C*2 + 2B + 2*B*ns << rows/64*C*2
+  // ws holds the parameter partials (nrb*C*2), the per-sample means (2B) and, on the split form, the
+  // chunk partials (2*B*ns).  avc_norm_ws(M, C) covers all three at the models' shapes (S large), but
+  // not for many samples of few elements (B = 300, S = 4: 1224 of 1064 floats): the chunk partials are
+  // then skipped (one block per sample writes the means directly), and a shape whose means alone do
+  // not fit is refused.
+  const size_t have = avc_norm_ws(M, C), base = (size_t)nrb * C * 2 + 2 * (size_t)B;
+  AVC_CHECK_ARG(B > 0 && base <= have,
+                "avc_group_norm_bwd: workspace of avc_norm_ws(%d, %d) floats cannot hold B = %d samples", M, C, B);
+  const bool vec = C % 4 == 0 && a16(dy) && a16(x) && a16(dx) && a16(gamma);
+  if (vec && base + 2 * (size_t)B * ns <= have) {
+    float* part = wsamp + 2 * B;
     const int chunk = (int)(((S + ns - 1) / ns + 3) / 4 * 4);
     gn_bwd_sample_part_kernel<<<dim3(ns, B), 256, 0, s>>>(dy, x, gamma, mean, rstd, S, C, chunk, part);
     gn_bwd_sample_final_kernel<<<cdiv(B, 64), 64, 0, s>>>(part, B, ns, S, wsamp);
+    gn_bwd_dx_v_kernel<<<cdiv(total / 4, 256), 256, 0, s>>>(dy, x, gamma, mean, rstd, wsamp, S, C, dx, total / 4);
+  } else if (vec) {
+    gn_bwd_sample_kernel<<<B, 1024, 0, s>>>(dy, x, gamma, mean, rstd, S, C, wsamp);
     gn_bwd_dx_v_kernel<<<cdiv(total / 4, 256), 256, 0, s>>>(dy, x, gamma, mean, rstd, wsamp, S, C, dx, total / 4);
   } else {
     gn_bwd_sample_kernel<<<B, 1024, 0, s>>>(dy, x, gamma, mean, rstd, S, C, wsamp);

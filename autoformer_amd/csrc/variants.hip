@@ -112,7 +112,7 @@ __global__ void __launch_bounds__(RED_THREADS) reduce2_final(const double* __res
       double mean = a / (double)n;
       double var = n > 1 ? (b - a * mean) / (double)(n - 1) : __builtin_nan("");
       out[0] = (float)mean;
-      out[1] = (float)sqrt(var > 0.0 ? var : 0.0);
+      out[1] = (float)sqrt(var < 0.0 ? 0.0 : var);  // clamps rounding below 0, keeps n = 1's NaN (torch.std)
     } else {
       out[0] = (float)a;
       out[1] = (float)b;

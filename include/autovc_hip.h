@@ -461,7 +461,9 @@ int avc_vc_loss_grad(const float* x, const float* y1, const float* y2, long long
                      const float* d2, const float* d3, float* g1, float* g2, float* ga, float* gb, void* stream);
 
 /* Activation-only passes (Discriminator's conv -> LeakyReLU -> BN order,
- * factory/Discriminator.py:18-29); the backward takes the activation OUTPUT. */
+ * factory/Discriminator.py:18-29); the backward takes the activation OUTPUT, so it refuses
+ * AVC_ACT_GELU (no derivative from the output: avc_gelu_bwd takes the input); both refuse a code
+ * outside AVC_ACT_*. */
 int avc_act_fwd(const float* x, float* y, long long n, int act, void* stream);
 int avc_act_bwd(const float* g, const float* yout, float* dx, long long n, int act, void* stream);
 

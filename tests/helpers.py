@@ -102,3 +102,59 @@ def bn_state_mismatches(model, g):
 
 def to_dev(g, dev, *keys):
     return [torch.from_numpy(g[k]).to(dev) for k in keys]
+
+
+# ---------------------------------------------------------------- direct-kernel bars (fp64 references)
+# Every helper returns error / bar, the worst element's: a test asserts `<= 1`, and the printed figure
+# says how far inside (or outside) its bar a kernel is.
+EPS32 = 2.0 ** -24   # unit roundoff of fp32 (round to nearest)
+BF16_ULP = 2.0 ** -8  # bf16 keeps 8 significand bits: round-to-nearest is within 2^-8, relative
+
+
+def f64(t):
+    return t.detach().cpu().double()
+
+
+def bits_equal(got, ref):
+    """Bit-for-bit equality (so -0.0 != 0.0 and equal NaNs compare equal); same dtype and shape."""
+    got, ref = got.detach().cpu().contiguous(), ref.detach().cpu().contiguous()
+    if got.dtype != ref.dtype or got.shape != ref.shape:
+        return False
+    it = {2: torch.int16, 4: torch.int32, 8: torch.int64}[got.element_size()]
+    return bool(torch.equal(got.view(it), ref.view(it)))
+
+
+def _ratio(err, bar):
+    """max err / bar with 0 / 0 = 0 and x / 0 = inf."""
+    r = torch.where(bar > 0, err / bar.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")),
+                                                                      torch.zeros_like(err)))
+    return float(r.max()) if r.numel() else 0.0
+
+
+def roundings_ratio(got, ref, k):
+    """Elementwise result of k fp32 roundings: |err| <= k * 2^-24 * |ref|."""
+    ref = ref.double()
+    return _ratio((f64(got).reshape(ref.shape) - ref).abs(), k * EPS32 * ref.abs())
+
+
+def sum_ratio(got, ref, sum_abs, d):
+    """fp32 sum whose terms pass through at most d dependent additions: |err| <= d * 2^-24 * sum|terms|."""
+    ref = ref.double()
+    return _ratio((f64(got).reshape(ref.shape) - ref).abs(), d * EPS32 * sum_abs.double().reshape(ref.shape))
+
+
+def close_ratio(got, ref, rtol, atol):
+    """torch.testing.assert_close's bar against a float64 reference: |err| <= atol + rtol * |ref|."""
+    ref = ref.double()
+    return _ratio((f64(got).reshape(ref.shape) - ref).abs(), atol + rtol * ref.abs())
+
+
+def rinf_ratio(got, ref, bar):
+    """max|err| / max|ref| over the bar (the rel-inf measure of the older direct tests)."""
+    return rel_inf(f64(got).reshape(ref.shape).numpy(), ref.double().numpy()) / bar
+
+
+def report(family, what, ratio):
+    """One line per check (pytest -s shows it): the measured error as a fraction of its bar."""
+    print(f"[direct] {family:10s} {what}: {ratio:.3g} of bar")
+    return ratio
