@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # AVC_LIB_PATH: another build of the same ABI (same-box A/B timing of two builds, tools/ only)
 LIB_PATH = os.environ.get("AVC_LIB_PATH") or os.path.join(HERE, "libautovc_hip.so")
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["gemm_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip"]
+SOURCES = ["gemm_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip"]
 ABI_VERSION = 31
 
 F32, BF16 = 0, 1
@@ -200,6 +200,20 @@ _SIGS = {
     "avc_gelu_twin": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p]),
 }
 
+# The MetaDV entry points of include/autovc_hip_dv.h: a second header and a second table, added without
+# an ABI bump (autovc_hip.h, ABI_VERSION and exported_symbols() are as they were); lib() binds both.
+c_int_p = ctypes.POINTER(c_int)
+_SIGS_DV = {
+    "avc_crop_windows": (c_int, [c_void_p, c_int, c_int_p, c_void_p, c_int_p, c_int, c_int, c_int, c_int, c_int,
+                                 c_void_p, c_int, c_void_p]),
+    "avc_crop_windows_bwd": (c_int, [c_void_p, c_void_p, c_int_p, c_void_p, c_int_p, c_void_p, c_int, c_int, c_int,
+                                     c_int, c_int, c_void_p, c_void_p]),
+    "avc_chan_mean": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "avc_chan_mean_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "avc_metadv_head": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                c_int, c_int, c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -211,7 +225,8 @@ def build(verbose: bool = False, force: bool = False) -> str:
         import glob
 
         # every header a translation unit includes (csrc/*.h, the public ABI header)
-        deps = srcs + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "autovc_hip.h")]
+        deps = srcs + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", h)
+                                                              for h in ("autovc_hip.h", "autovc_hip_dv.h")]
         newest = max(os.path.getmtime(p) for p in deps)
         if os.path.getmtime(LIB_PATH) >= newest:
             return LIB_PATH
@@ -247,7 +262,7 @@ def lib():
             raise RuntimeError(f"libautovc_hip.so not found at {LIB_PATH}; run autoformer_amd._lib.build() "
                                "(or __graft_entry__.build()). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_DV.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -283,3 +298,8 @@ def call(name: str, *args) -> None:
 
 def exported_symbols():
     return list(_SIGS.keys())
+
+
+def exported_symbols_dv():
+    """The entry points of include/autovc_hip_dv.h (the MetaDV kernels)."""
+    return list(_SIGS_DV.keys())

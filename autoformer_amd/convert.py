@@ -40,7 +40,7 @@ class Converter:
         self.len_crop = len_crop
         self.device = torch.device(device)
         self.vocoder = vocoder  # autoformer_amd.melgan.MelVocoder (evaluate.py:24) or None
-        self.embedder = embedder  # factory.LstmDV.LstmDV (evaluate.py:25) or None: convert_between
+        self.embedder = embedder  # an LstmDV (evaluate.py:25), a MetaDV or None: convert_between
 
     @torch.no_grad()
     def get_wavs(self, mel, frames: bool = False):

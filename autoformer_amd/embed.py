@@ -1,4 +1,5 @@
-"""Speaker embeddings from mel-spectrograms with the LstmDV d-vector net (factory/LstmDV.py): what
+"""Speaker embeddings from mel-spectrograms with the LstmDV d-vector net (factory/LstmDV.py) or the
+MetaDV classifier (factory/MetaDV.py, `--embedder MetaDV`): what
 the reference does in make_data/make_metadata.ipynb (the `train.pkl` speaker entries) and in the
 second half of util/evaluate.py (get_dv :100-106, the cosine scores :140-146, :205-211).
 
@@ -15,7 +16,14 @@ member, and `lens` tells the model which frame is each row's last (rows are inde
 padding past a row's own length never reaches its embedding).
 
 `model` is any callable (x (B, T, 80) tensor, lens list) -> (B, E) tensor; an LstmDV is called under
-torch.no_grad() on its own device.
+torch.no_grad() on its own device.  An embedder that returns a tuple -- MetaDV's (predictions, d_vec) --
+contributes its last entry, the d-vector.  One with a `crop_len` of its own (MetaDV cuts 128-frame
+windows) refuses a `len_crop` below it: a shorter utterance would be padded to less than one window.
+
+MetaDV draws its windows from Python's `random`, one utterance's crops after another's within a
+batch, and the batches are sorted by length: the batched call therefore does NOT reproduce the draw
+order of the reference's one-utterance-at-a-time loop.  `lefts` (one row of window starts per
+utterance, in input order) fixes the windows and gives exact parity with single-utterance calls.
 
   python -m autoformer_amd.embed --spmel DIR --ckpt FILE --out train.pkl
 """
@@ -60,12 +68,20 @@ def _batch_cap(model, max_batch):
 
 
 @torch.no_grad()
-def embed_utterances(model, mels, len_crop=176, max_batch=None):
+def embed_utterances(model, mels, len_crop=176, max_batch=None, lefts=None):
     """(N, E) float32 embeddings of the utterances `mels` (each (T_i, 80)), in input order.
-    max_batch None: what model.max_infer_batch() admits per launch (64 for a plain callable)."""
+    max_batch None: what model.max_infer_batch() admits per launch (64 for a plain callable).
+    lefts (an embedder that crops windows only): per utterance, in input order, its window starts;
+    None lets the embedder draw them (not in the reference's per-utterance order, see above)."""
+    need = getattr(model, "crop_len", None)
+    if need is not None and len_crop < int(need):
+        raise ValueError(f"len_crop = {len_crop} is below the embedder's crop_len = {int(need)}: an utterance padded "
+                         f"to {len_crop} frames is shorter than one of its windows")
     mels = [_pad_short(m, len_crop) for m in mels]
     if not mels:
         raise ValueError("embed_utterances: no utterances")
+    if lefts is not None and len(lefts) != len(mels):
+        raise ValueError(f"lefts must hold one row of window starts per utterance ({len(mels)}), got {len(lefts)}")
     cap = _batch_cap(model, max_batch)
     dev = _model_device(model)
     order = sorted(range(len(mels)), key=lambda i: mels[i].shape[0])  # stable: ties keep input order
@@ -79,7 +95,12 @@ def embed_utterances(model, mels, len_crop=176, max_batch=None):
         xt = torch.from_numpy(x)
         if dev is not None:
             xt = xt.to(dev)
-        emb = model(xt, lens)
+        if lefts is None:
+            emb = model(xt, lens)
+        else:  # the embedder takes crops-major rows: sample_count rows of B starts
+            emb = model(xt, lens, lefts=[list(col) for col in zip(*[lefts[i] for i in idx])])
+        if isinstance(emb, (tuple, list)):
+            emb = emb[-1]  # (predictions, d_vec): the d-vector
         emb = emb.detach().float().cpu().numpy()
         if dev is not None and dev.type == "cuda":
             from . import kernels as K
@@ -92,10 +113,10 @@ def embed_utterances(model, mels, len_crop=176, max_batch=None):
     return np.stack(out).astype(np.float32)
 
 
-def speaker_dvector(model, mels, len_crop=176, max_batch=None):
+def speaker_dvector(model, mels, len_crop=176, max_batch=None, lefts=None):
     """The speaker's d-vector (E,): the mean of its utterances' embeddings, not renormalised
     (make_metadata.ipynb cell 5 np.mean(embs, axis=0); evaluate.py:100-106)."""
-    return embed_utterances(model, mels, len_crop, max_batch).mean(axis=0)
+    return embed_utterances(model, mels, len_crop, max_batch, lefts).mean(axis=0)
 
 
 def build_metadata(root, model, num_uttrs=68, len_crop=176, max_batch=None):
@@ -134,7 +155,9 @@ def _parser():
                                 description="speaker d-vectors + train.pkl for a folder of mel-spectrograms "
                                             "(make_data/make_metadata.ipynb)")
     p.add_argument("--spmel", required=True, help="folder with one sub-folder of (T, 80) .npy mels per speaker")
-    p.add_argument("--ckpt", help="LstmDV state_dict (torch.save); required unless --det_init")
+    p.add_argument("--embedder", choices=["LstmDV", "MetaDV"], default="LstmDV", help="the speaker embedder")
+    p.add_argument("--num_classes", type=int, default=256, help="MetaDV: classes of its checkpoint's classifier head")
+    p.add_argument("--ckpt", help="the embedder's state_dict (torch.save); required unless --det_init")
     p.add_argument("--out", help="metadata file to write (default: <spmel>/train.pkl)")
     p.add_argument("--num_uttrs", type=int, default=68)
     p.add_argument("--len_crop", type=int, default=176)
@@ -149,12 +172,20 @@ def main(argv=None):
     if not str(args.device).startswith("cuda"):
         raise SystemExit(f"--device {args.device}: the HIP kernels need a GPU")
     if not args.ckpt and not args.det_init:
-        raise SystemExit("--ckpt FILE (an LstmDV state_dict) is required unless --det_init is given")
+        raise SystemExit(f"--ckpt FILE (an {args.embedder} state_dict) is required unless --det_init is given")
     import autoformer_amd as A
-    from .factory.LstmDV import LstmDV
 
     A.set_compute(args.dtype)
-    model = LstmDV()
+    if args.embedder == "MetaDV":
+        from .factory.MetaDV import MetaDV
+
+        model = MetaDV(args.num_classes)
+        if args.len_crop < model.crop_len:
+            raise SystemExit(f"--len_crop {args.len_crop} is below MetaDV's crop_len = {model.crop_len}")
+    else:
+        from .factory.LstmDV import LstmDV
+
+        model = LstmDV()
     if args.det_init:
         from .detinit import det_init_
 

@@ -1150,3 +1150,107 @@ def gelu_bwd_twin(g, x):
     d16 = _twin_buf(dx, None)
     L.call("avc_gelu_twin", g.data_ptr(), x.data_ptr(), dx.data_ptr(), _ptr(d16), x.numel(), 1, stream())
     return attach_twin(dx, d16)
+
+
+# ------------------------------------------------------------------------- MetaDV (autovc_hip_dv.h)
+class Lefts:
+    """Window starts of S crops of B utterances: the host integers (checked by the library before
+    each launch) and the same values as an int32 device tensor (read by the kernels); `last` the
+    same way for each utterance's own last frame (None: T - 1)."""
+
+    def __init__(self, lefts, S, B, device, last=None):
+        flat = [int(v) for row in lefts for v in row]
+        if len(lefts) != S or len(flat) != S * B:
+            raise ValueError(f"lefts must hold S={S} rows of B={B} window starts")
+        self.S, self.B = S, B
+        self.host = (L.c_int * (S * B))(*flat)
+        self.dev = torch.tensor(flat, dtype=torch.int32, device=device)
+        self.last_host = self.last_dev = None
+        if last is not None:
+            last = [int(v) for v in last]
+            if len(last) != B:
+                raise ValueError(f"last must hold B={B} frame indices")
+            self.last_host = (L.c_int * B)(*last)
+            self.last_dev = torch.tensor(last, dtype=torch.int32, device=device)
+
+
+def crop_windows(h, lf: Lefts, B, T, W, lens=None, dtype=None):
+    """X (S*B*E, W) with X[(s*B+b)*E + l][c] = h[b][left[s][b] + c][l] from the frame-major h (B*T, E),
+    fp32 or bf16, in `dtype` (default: the compute dtype; a bf16 h gives bf16).  lens: host frame
+    counts (every start must lie in 0..lens[b] - W)."""
+    _dev(h)
+    E = h.shape[1]
+    if h.dim() != 2 or h.shape[0] != B * T or not h.is_contiguous() or lf.B != B or lf.dev.device != h.device:
+        raise ValueError("crop_windows: h must be a contiguous (B*T, E) tensor on the device of its window starts")
+    dtype = (BF16 if h.dtype == torch.bfloat16 else _COMPUTE) if dtype is None else dtype
+    larr = None
+    if lens is not None:
+        lens = [int(v) for v in lens]
+        if len(lens) != B:
+            raise ValueError(f"crop_windows: lens must hold B={B} values")
+        larr = (L.c_int * B)(*lens)
+    X = torch.empty(lf.S * B * E, W, device=h.device, dtype=torch.bfloat16 if dtype == BF16 else torch.float32)
+    L.call("avc_crop_windows", h.data_ptr(), _dt(h), lf.host, lf.dev.data_ptr(), larr, B, T, E, W, lf.S, X.data_ptr(),
+           dtype, stream())
+    return X
+
+
+def crop_windows_bwd(dX, de1, lf: Lefts, B, T, E):
+    """dh (B*T, E) fp32, every element written: the sum over the crops covering each frame of
+    dX (S*B*E, W) fp32, plus de1 (B, E) at each utterance's last frame (lf.last, default T - 1)."""
+    _dev(dX, de1)
+    W = dX.shape[1]
+    if dX.dtype != torch.float32 or tuple(dX.shape) != (lf.S * B * E, W) or not dX.is_contiguous():
+        raise ValueError("crop_windows_bwd: dX must be a contiguous fp32 (S*B*E, W) tensor")
+    if de1 is not None and (de1.dtype != torch.float32 or tuple(de1.shape) != (B, E) or not de1.is_contiguous()):
+        raise ValueError("crop_windows_bwd: de1 must be a contiguous fp32 (B, E) tensor")
+    dh = torch.empty(B * T, E, device=dX.device)
+    L.call("avc_crop_windows_bwd", dX.data_ptr(), _ptr(de1), lf.host, lf.dev.data_ptr(), lf.last_host,
+           _ptr(lf.last_dev), B, T, E, W, lf.S, dh.data_ptr(), stream())
+    return dh
+
+
+def _chan_shape(Y, S, B, who):
+    if Y.dtype != torch.float32 or Y.dim() != 2 or not Y.is_contiguous() or Y.shape[0] % (S * B):
+        raise ValueError(f"{who}: Y must be a contiguous fp32 (S*B*E, O) tensor")
+    return Y.shape[0] // (S * B), Y.shape[1]
+
+
+def chan_mean(Y, S, B):
+    """e2 (B, E): the mean over the S crops of column O - 1 of the mixer output Y (S*B*E, O)."""
+    _dev(Y)
+    E, O = _chan_shape(Y, S, B, "chan_mean")
+    e2 = torch.empty(B, E, device=Y.device)
+    L.call("avc_chan_mean", Y.data_ptr(), S, B, E, O, e2.data_ptr(), stream())
+    return e2
+
+
+def chan_mean_bwd(g, S, O):
+    """dY (S*B*E, O), all of it: g / S in column O - 1, zero elsewhere."""
+    _dev(g)
+    if g.dtype != torch.float32 or g.dim() != 2 or not g.is_contiguous():
+        raise ValueError("chan_mean_bwd: g must be a contiguous fp32 (B, E) tensor")
+    B, E = g.shape
+    dY = torch.empty(S * B * E, O, device=g.device)
+    L.call("avc_chan_mean_bwd", g.data_ptr(), S, B, E, O, dY.data_ptr(), stream())
+    return dY
+
+
+def metadv_head(e1, Y, S, w_dv, b_dv, w_out, b_out):
+    """(pred (B, C), d_vec (B, D)) of the forward-only MetaDV head (avc_metadv_head), fp32:
+    emb = W_dv cat(e1, chan_mean(Y)) + b_dv, d_vec = emb / ||emb||, pred = W_out emb + b_out."""
+    _dev(e1, Y, w_dv, b_dv, w_out, b_out)
+    B, E = e1.shape
+    _, O = _chan_shape(Y, S, B, "metadv_head")
+    D, C = w_dv.shape[0], w_out.shape[0]
+    ok = all(t.dtype == torch.float32 and t.is_contiguous() for t in (e1, w_dv, w_out))
+    if not ok or Y.shape[0] != S * B * E or tuple(w_dv.shape) != (D, 2 * E) or tuple(w_out.shape) != (C, D):
+        raise ValueError("metadv_head: e1 (B, E), Y (S*B*E, O), W_dv (D, 2E), W_out (C, D), contiguous fp32")
+    for bias, n in ((b_dv, D), (b_out, C)):
+        if bias is not None and (bias.dtype != torch.float32 or bias.numel() != n or not bias.is_contiguous()):
+            raise ValueError("metadv_head: a bias must be a contiguous fp32 vector of its layer's width")
+    pred = torch.empty(B, C, device=e1.device)
+    dvec = torch.empty(B, D, device=e1.device)
+    L.call("avc_metadv_head", e1.data_ptr(), Y.data_ptr(), S, O, w_dv.data_ptr(), _ptr(b_dv), w_out.data_ptr(),
+           _ptr(b_out), B, E, D, C, pred.data_ptr(), dvec.data_ptr(), stream())
+    return pred, dvec
