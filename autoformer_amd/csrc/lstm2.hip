@@ -51,6 +51,40 @@ constexpr size_t persist2_lds() {
          (size_t)8 * NLW * 64 * 16 + (size_t)6 * 512 * 4 + 16;
 }
 
+// ---- LDS-DMA staging of the backward's hand-off payload: 16-B global_load_lds fills, sc1 like every
+// other load of handed-off bytes, retired by counted s_waitcnt vmcnt(n) + s_barrier.
+__device__ __attribute__((aligned(16))) unsigned g_zero16_l2[4] = {0u, 0u, 0u, 0u};  // source of zero rows
+typedef __attribute__((address_space(3))) void* l2_lds_ptr;
+typedef const __attribute__((address_space(1))) void* l2_gbl_ptr;
+// 16-B LDS fragment read as inline asm: the compiler's waitcnt pass would otherwise wait for every
+// LDS-DMA in flight (the next chunk's) before it
+__device__ __forceinline__ bf16x8 l2_ds_read16(unsigned addr) {
+  u32x4_t v;
+  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
+  return __builtin_bit_cast(bf16x8, v);
+}
+// the block's quit word, read the same way: before a plain LDS read the compiler waits for the previous
+// tick's fills with a count that also covers the output stores issued after them
+__device__ __forceinline__ int l2_ds_read_word(unsigned addr) {
+  int v;
+  asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
+  return v;
+}
+__device__ __forceinline__ unsigned l2_lds_addr(const void* p) {
+  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
+}
+// workgroup barrier for LDS traffic alone: __syncthreads() also waits for every global load and store
+// of the wave (vmcnt(0)).  (Backward only: its output stores follow the publication.  In the forward,
+// whose output stores precede it, the same barriers let them queue in front of wave 0's payload stores:
+// measured slower, profiles/r7_recur_fetch_ab.txt.)
+__device__ __forceinline__ void l2_lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+// at most N vector-memory operations of this wave still in flight
+template <int N>
+__device__ __forceinline__ void l2_wait_vm() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
 // Waves 1..7: the staged outputs of tick kp (all 512 cells) to HBM.  (16-B value-major stores
 // of the same bytes measured slower per tick: 5.18 vs 4.99 us.)
 template <int H>
@@ -283,17 +317,6 @@ constexpr size_t persist2_bwd_lds() {
   return (size_t)2 * 2 * QRG * BCP * 2 + (size_t)8 * BNLW * 64 * 16 + 16;
 }
 
-__device__ __attribute__((aligned(16))) unsigned g_zero16_l2[4] = {0u, 0u, 0u, 0u};
-typedef __attribute__((address_space(3))) void* l2_lds_ptr;
-typedef const __attribute__((address_space(1))) void* l2_gbl_ptr;
-// 16-B LDS fragment read as inline asm: the compiler's waitcnt pass would otherwise wait for every
-// LDS-DMA in flight (the next chunk's) before it
-__device__ __forceinline__ bf16x8 l2_ds_read16(unsigned addr) {
-  u32x4_t v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-  return __builtin_bit_cast(bf16x8, v);
-}
-
 template <int H>
 __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
   constexpr int G = 4 * H, NR = H / QJU, KPW = BKC / 32 / 8, NF0 = BNC * KPW - BNLW;
@@ -347,35 +370,39 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
     }
   };
   if (tid == 0) *quit = 0;
-  const int L = tid >> 8, cr = (tid >> 4) & 15, cu = tid & 15, cb = b0 + cr, cj = j0 + cu;
+  const int L = w >> 2, cr = (tid >> 4) & 15, cu = tid & 15, cb = b0 + cr, cj = j0 + cu;  // (L wave-uniform)
   const bool cv = cb < B;
   const unsigned aoff = (unsigned)(((lane & 15) * BCP + w * KPW * 32 + 8 * (lane >> 4)) * 2);
   float dc = 0.f;
   float sb0 = 0.f, sb1 = 0.f, sb2 = 0.f, sb3 = 0.f;  // this cell's dG summed over its steps (dbp)
+  const unsigned quit_addr = l2_lds_addr(quit);
   __syncthreads();
 
   for (int k = 0; k <= T; ++k) {
     const int t = L == 1 ? T - 1 - k : T - k;  // this thread's step
     const bool act = (L == 1 ? k < T : k >= 1) && cv;
     if (k < T) stamp(a.trace, T, k, 0);
-    // per-cell inputs of this step (independent of the exchange: issued first)
+    f32x4 p1 = {0.f, 0.f, 0.f, 0.f}, p0 = {0.f, 0.f, 0.f, 0.f};
+    // per-cell inputs of this step (independent of the exchange: issued first).  The layer's pointers
+    // come by select on the wave-uniform L: indexed by a per-thread L they were loaded from the argument
+    // block through vector memory, each with a wait for everything older, on every tick.
     float dhu = 0.f, ct = 0.f, cp = 0.f, gi = 0.f, gf = 0.f, gg = 0.f, go = 0.f;
     if (act) {
+      const float* callL = L ? a.call[1] : a.call[0];
       const long long oh = ((long long)cb * T + t) * H + cj;
       if (L == 1) dhu = a.dhout1[oh];
-      ct = a.call[L][oh];
-      cp = t > 0 ? a.call[L][oh - H] : 0.f;
-      const float* gp = a.gall[L] + ((long long)cb * T + t) * G + cj;
+      ct = callL[oh];
+      cp = t > 0 ? callL[oh - H] : 0.f;
+      const float* gp = (L ? a.gall[1] : a.gall[0]) + ((long long)cb * T + t) * G + cj;
       gi = gp[0];
       gf = gp[H];
       gg = gp[2 * H];
       go = gp[3 * H];
     }
-    f32x4 p1 = {0.f, 0.f, 0.f, 0.f}, p0 = {0.f, 0.f, 0.f, 0.f};
     if (k > 0) {
       if (w == 0 && !poll_flags(flags, NR, (unsigned)k, a.ctl, a.fault, a.spin)) *quit = 1;
       __syncthreads();
-      if (*quit) return;  // block-uniform exit after a spin timeout
+      if (l2_ds_read_word(quit_addr)) return;  // block-uniform exit after a spin timeout
       if (k < T) stamp(a.trace, T, k, 1);
       const int slot = (k - 1) & 1;
       issue(0, slot);
@@ -384,8 +411,8 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
       for (int c = 0; c < BNC; ++c) {
         // this wave's fills of chunk c have landed (the next chunk's 8 may be in flight), then
         // every wave's
-        if (c < BNC - 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (c < BNC - 1) l2_wait_vm<8>();
+        else l2_wait_vm<0>();
         asm volatile("s_barrier" ::: "memory");
         const unsigned base = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)(smem_raw + (c & 1) * CB) + aoff;
         // XB k-blocks of A fragments at a time (the weight fragments hold ~180 VGPRs)
@@ -420,7 +447,7 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
       red[((w * 2 + 0) * QRG + 4 * (lane >> 4) + e) * QJU + (lane & 15)] = p0[e];
       red[((w * 2 + 1) * QRG + 4 * (lane >> 4) + e) * QJU + (lane & 15)] = p1[e];
     }
-    __syncthreads();
+    l2_lds_barrier();
     if (k < T) stamp(a.trace, T, k, 2);
     float dh = dhu;
 #pragma unroll
@@ -444,7 +471,7 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
     dsr[QJU] = (bf16)v1;
     dsr[2 * QJU] = (bf16)v2;
     dsr[3 * QJU] = (bf16)v3;
-    __syncthreads();
+    l2_lds_barrier();
     // ---- publish dG1_{t1} and dG0_{t0} (needed by tick k + 1; none after tick T - 1): wave 0, four
     // 16-B chunks per lane (2 layers x 16 rows x 8 chunks), then the flag
     if (w == 0 && k < T) {
@@ -463,15 +490,17 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
                       // output instead measured slower, profiles/r6_lstm2_bwd_payload_out.txt)
     if (act) {  // (wave 0 issues these after its flag: they stay off the hand-off's vmcnt wait)
       const long long og = ((long long)cb * T + t) * G + cj;
-      if (a.dg[L]) {
-        float* d = a.dg[L] + og;
+      float* dgL = L ? a.dg[1] : a.dg[0];
+      bf16* dg16L = L ? a.dg16[1] : a.dg16[0];
+      if (dgL) {
+        float* d = dgL + og;
         d[0] = v0;
         d[H] = v1;
         d[2 * H] = v2;
         d[3 * H] = v3;
       }
-      if (a.dg16[L]) {
-        bf16* d16 = a.dg16[L] + og;
+      if (dg16L) {
+        bf16* d16 = dg16L + og;
         d16[0] = (bf16)v0;
         d16[H] = (bf16)v1;
         d16[2 * H] = (bf16)v2;
