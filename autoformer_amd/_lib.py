@@ -105,6 +105,7 @@ _SIGS = {
     "avc_lstm_set_spin": (c_int, [ctypes.c_uint]),
     "avc_gemm_set_ring": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "avc_gemm_ring_last": (c_int, []),
+    "avc_gemm_last_path": (c_int, []),
     "avc_lstm2_bwd_persistent": (c_int, [c_int, c_int, c_int]),
     "avc_lstm2_bwd_scratch_bytes": (c_size, [c_int, c_int]),
     "avc_lstm2_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
@@ -199,6 +200,14 @@ _SIGS = {
     "avc_pad_cols": (c_int, [c_void_p, c_ll, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "avc_gelu_twin": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p]),
 }
+
+# avc_gemm_last_path's encoding (the AVC_PATH_* enum of include/autovc_hip.h): family in bits 0-3,
+# variant in bits 4-7 (fast / nt: 1 = 64-column tiles, 2 = 128; tt: 1 plain, 2 window stream, 3 halo;
+# ring: avc_gemm_ring_last's 1 gemm / 2 halo conv / 3 one-utterance conv), then the flag bits.
+PATH_GENERIC, PATH_FAST, PATH_NT, PATH_CONV, PATH_TT, PATH_RING = 1, 2, 3, 4, 5, 6
+PATH_VARIANT_SHIFT = 4
+PATH_SPLITK_WS, PATH_POST_PASS, PATH_WINDOW, PATH_BNB = 0x100, 0x200, 0x400, 0x800
+
 
 # The MetaDV entry points of include/autovc_hip_dv.h: a second header and a second table, added without
 # an ABI bump (autovc_hip.h, ABI_VERSION and exported_symbols() are as they were); lib() binds both.

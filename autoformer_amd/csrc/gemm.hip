@@ -825,7 +825,10 @@ static int gelu_after(const GemmArgs& g, const GeluPost& p, hipStream_t s, bool 
   return 0;
 }
 
+thread_local int avcg::g_gemm_path = 0;  // avc_gemm_last_path
+
 static int gemm_impl(const avc_gemm_desc* d, const avc_bn_fin* f, void* stream, const avc_bnb_args* bb = nullptr) {
+  g_gemm_path = 0;
   AVC_CHECK_ARG(d != nullptr, "avc_gemm: null desc");
   AVC_CHECK_ARG(d->M >= 0 && d->N >= 0 && d->K >= 0, "avc_gemm: negative dims");
   if (d->M == 0 || d->N == 0) return 0;
@@ -980,9 +983,12 @@ static int gemm_impl(const avc_gemm_desc* d, const avc_bn_fin* f, void* stream, 
     if (ring) what = "avc_gemm(ring)";
     else post = strip_gelu(g);  // the other kernels have no GELU epilogue: a pass after them
     if (ring) {
-    } else if (!aks && !bks && gemm_conv_launch(g, s)) what = "avc_gemm(conv)";
-    else if (!aks && !bks && gemm_nt_launch(g, s)) what = "avc_gemm(nt)";
-    else if (aks && bks && gemm_tt_launch(g, s)) what = "avc_gemm(tt)";
+      g_gemm_path = AVC_PATH_RING | (avc_gemm_ring_last() << AVC_PATH_VARIANT_SHIFT);
+    } else if (!aks && !bks && gemm_conv_launch(g, s)) {
+      what = "avc_gemm(conv)";
+      g_gemm_path = AVC_PATH_CONV;
+    } else if (!aks && !bks && gemm_nt_launch(g, s)) what = "avc_gemm(nt)";  // (sets its own record)
+    else if (aks && bks && gemm_tt_launch(g, s)) what = "avc_gemm(tt)";    // (sets its own record)
     else {
       gemm_zero_c(g, s);
       const long long t128 = (long long)cdiv(g.M, BM) * cdiv(g.N, 128) * g.batch * g.split_k;
@@ -990,8 +996,14 @@ static int gemm_impl(const avc_gemm_desc* d, const avc_bn_fin* f, void* stream, 
       const int nb = narrow ? cdiv(g.M, BM) * cdiv(g.N, 64) * g.batch * g.split_k : (int)t128;
       if (narrow) launch_fast_layout<64>(g, aks, bks, nb, s);
       else launch_fast_layout<128>(g, aks, bks, nb, s);
+      g_gemm_path = AVC_PATH_FAST | ((narrow ? 1 : 2) << AVC_PATH_VARIANT_SHIFT);
     }
-    if (avc_check_launch(what)) return -1;
+    if (g.bnb_ws) g_gemm_path |= AVC_PATH_BNB;
+    if (post.act || post.agrad || post.csum) g_gemm_path |= AVC_PATH_POST_PASS;
+    if (avc_check_launch(what)) {
+      g_gemm_path = 0;  // the launch failed: nothing ran
+      return -1;
+    }
     if (ring && g.csum_ws) {
       const int nc = g.csum_n > 0 ? g.csum_n : g.N;
       colsum_slots_kernel<<<cdiv(nc, 256), 256, 0, s>>>(g.csum_ws, g.csum_slots, nc, g.csum);
@@ -1031,6 +1043,7 @@ static int gemm_impl(const avc_gemm_desc* d, const avc_bn_fin* f, void* stream, 
   }
 #undef AVC_GEMM_LAUNCH
   if (avc_check_launch("avc_gemm")) return -1;
+  g_gemm_path = AVC_PATH_GENERIC | ((post.act || post.agrad || post.csum) ? AVC_PATH_POST_PASS : 0);
   if (gelu_after(g, post, s, true)) return -1;
   if (bb && bnb_after(d, bb, s)) return -1;
   if (f && bn_finalize_after(g, f, stream)) return -1;  // generic kernels: finalize launch(es) after the GEMM
@@ -1039,12 +1052,15 @@ static int gemm_impl(const avc_gemm_desc* d, const avc_bn_fin* f, void* stream, 
 
 extern "C" int avc_gemm(const avc_gemm_desc* d, void* stream) { return gemm_impl(d, nullptr, stream); }
 
+extern "C" int avc_gemm_last_path(void) { return avcg::g_gemm_path; }
+
 extern "C" size_t avc_gemm_bnb_ws(int M, int N) {
   // fused: cdiv(M, 128) row tiles; fallback pass: cdiv(M, 64) row blocks; 3 sums each
   return (size_t)cdiv(M, 64) * N * 3;
 }
 
 extern "C" int avc_gemm_bnb(const avc_gemm_desc* d, const avc_bnb_args* bb, void* stream) {
+  avcg::g_gemm_path = 0;  // a call refused here reads 0 as well
   AVC_CHECK_ARG(d != nullptr && bb != nullptr, "avc_gemm_bnb: null args");
   AVC_CHECK_ARG(bb->y && bb->mean && bb->rstd && bb->coef && bb->ws && (bb->y_dtype == AVC_F32 || bb->y_dtype == AVC_BF16),
                 "avc_gemm_bnb: needs y, mean, rstd, coef, ws");
@@ -1056,6 +1072,7 @@ extern "C" int avc_gemm_bnb(const avc_gemm_desc* d, const avc_bnb_args* bb, void
 }
 
 extern "C" int avc_gemm_bn(const avc_gemm_desc* d, const avc_bn_fin* f, void* stream) {
+  avcg::g_gemm_path = 0;
   AVC_CHECK_ARG(f != nullptr, "avc_gemm_bn: null finalize args");
   return gemm_impl(d, f, stream);
 }

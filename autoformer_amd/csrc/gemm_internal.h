@@ -446,5 +446,7 @@ float* gemm_splitk_ws(size_t bytes, hipStream_t s);
 // Entry of the 8-wave deep-ring NT kernel (gemm_ring.hip); false when the shape / operands do
 // not qualify or AVC_RING=0.
 bool gemm_ring_launch(const GemmArgs& g, hipStream_t s);
+// avc_gemm_last_path: what this thread's last gemm_impl launched (AVC_PATH_*; host only; gemm.hip)
+extern thread_local int g_gemm_path;
 
 }  // namespace avcg

@@ -224,6 +224,7 @@ bool gemm_nt_launch(const GemmArgs& g, hipStream_t s) {
   if (nst < 2 || nst > 4) nst = 2;
   const int nb = ((g.M + BM - 1) / BM) * ((g.N + bn - 1) / bn) * g.batch * g.split_k;
   const bool win = g.a.win != 0;
+  g_gemm_path = AVC_PATH_NT | ((bn == 128 ? 2 : 1) << AVC_PATH_VARIANT_SHIFT) | (win ? AVC_PATH_WINDOW : 0);
   if (g.bnb_ws) {  // BN-backward epilogue: two-stage instances only
     if (bn == 128) {
       if (win) launch<128, 2, true, true>(g, nb, s);
@@ -242,6 +243,7 @@ bool gemm_nt_launch(const GemmArgs& g, hipStream_t s) {
   }
   NT_CASE(128, 2) NT_CASE(128, 3) NT_CASE(128, 4) NT_CASE(64, 2) NT_CASE(64, 3) NT_CASE(64, 4)
 #undef NT_CASE
+  g_gemm_path = 0;
   return false;
 }
 

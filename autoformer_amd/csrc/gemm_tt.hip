@@ -492,6 +492,7 @@ bool gemm_tt_launch(const GemmArgs& g0, hipStream_t s) {
     fixup(((g.M + BM - 1) / BM) * (x.chans / 32), (size_t)BM * 32 * x.taps * 4);
     gemm_zero_c(ga, s);
     launch_halo<2>(g, s);  // two LDS stages (three measured no faster)
+    g_gemm_path = AVC_PATH_TT | (3 << AVC_PATH_VARIANT_SHIFT) | (g.sk_ws ? AVC_PATH_SPLITK_WS : 0);
     return true;
   }
   fixup(((g.M + BM - 1) / BM) * ((g.N + 127) / 128), (size_t)BM * 128 * 4);
@@ -499,6 +500,7 @@ bool gemm_tt_launch(const GemmArgs& g0, hipStream_t s) {
   const int nb = ((g.M + BM - 1) / BM) * ((g.N + 127) / 128) * g.batch * g.split_k;
   if (g.b.win) launch<true>(g, nb, s);
   else launch<false>(g, nb, s);
+  g_gemm_path = AVC_PATH_TT | ((g.b.win ? 2 : 1) << AVC_PATH_VARIANT_SHIFT) | (g.sk_ws ? AVC_PATH_SPLITK_WS : 0);
   return true;
 }
 

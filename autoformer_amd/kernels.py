@@ -207,6 +207,12 @@ def gemm(M, N, K, a: L.Operand, b: L.Operand, c: torch.Tensor, ldc=None, bias=No
     return stats
 
 
+def gemm_last_path() -> int:
+    """What this thread's last gemm() launched (avc_gemm_last_path: _lib.PATH_*; 0 = nothing).  A host
+    read of a thread-local: called directly, not through _lib.call, so a recorded step never holds it."""
+    return int(L.lib().avc_gemm_last_path())
+
+
 _TT_SPLITK_MAX = int(os.environ.get("AVC_TT_SPLITK", "8") or 0)
 
 

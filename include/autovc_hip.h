@@ -337,9 +337,32 @@ int avc_lstm2_bwd(const float* dh1, const float* c0, const float* gates0, const 
 
 /* Which deep-ring kernel the last avc_gemm on this host thread launched (tests, tools): 0 none (an
  * older kernel), 1 gemm_ring_kernel, 2 the 128-row halo conv (conv_ring_kernel, its BN-backward
- * form included), 3 the one-utterance halo conv (conv_utt_kernel, 128 < T <= 192), 4 the
- * warp-specialised halo conv, 5 the 32-deep-slot ring.  Replaces no reference interface. */
+ * form included), 3 the one-utterance halo conv (conv_utt_kernel, 128 < T <= 192).  (The
+ * warp-specialised halo conv and the 32-deep-slot ring, once 4 and 5, no longer exist: a forced
+ * configuration the ring has no instance for is declined.)  Replaces no reference interface. */
 int avc_gemm_ring_last(void);
+
+/* Which kernel the last avc_gemm / avc_gemm_bn / avc_gemm_bnb on this host thread launched (tests,
+ * tools; no ABI bump: a new symbol only).  Host-only and thread-local: no device work, no kernel
+ * argument.  0 = nothing ran: the call was refused, M == 0 or N == 0, or the
+ * kernel's launch failed.  Otherwise
+ *   bits 0-3  family : 1 generic kernel (gemm.hip), 2 gemm_fast_kernel, 3 gemm_nt.hip,
+ *                      4 gemm_conv.hip, 5 gemm_tt.hip, 6 the ring kernels (gemm_ring.hip)
+ *   bits 4-7  variant: fast / nt: 1 = 64-column tiles, 2 = 128-column tiles;
+ *                      tt: 1 plain, 2 window stream, 3 halo;
+ *                      ring: avc_gemm_ring_last's value (1 gemm, 2 halo conv, 3 one-utterance conv);
+ *                      generic / conv: 0
+ *   0x100  split-K partials reduced through the workspace by the last split (tt), not by atomics
+ *   0x200  a GELU / col_sum pass ran after the kernel (the kernel has no such epilogue)
+ *   0x400  the instance streams a frame-window A operand as im2col (nt)
+ *   0x800  the BatchNorm-backward reduction of avc_gemm_bnb ran in the kernel's epilogue
+ * Replaces no reference interface. */
+enum {
+  AVC_PATH_GENERIC = 1, AVC_PATH_FAST = 2, AVC_PATH_NT = 3, AVC_PATH_CONV = 4, AVC_PATH_TT = 5, AVC_PATH_RING = 6,
+  AVC_PATH_VARIANT_SHIFT = 4,
+  AVC_PATH_SPLITK_WS = 0x100, AVC_PATH_POST_PASS = 0x200, AVC_PATH_WINDOW = 0x400, AVC_PATH_BNB = 0x800
+};
+int avc_gemm_last_path(void);
 
 /* 1 when avc_lstm_fwd (backward = 0) / avc_lstm_bwd (backward = 1) take the one-launch
  * persistent path for this shape on the current device: bf16 compute, dirs == 1, H in

@@ -55,6 +55,7 @@ def test_argument_validation_without_gpu(lib):
     rc = lib.avc_gemm(None, None)
     assert rc != 0
     assert b"null" in lib.avc_last_error()
+    assert lib.avc_gemm_last_path() == 0  # a refused call launched nothing
     with pytest.raises(RuntimeError):
         _lib.check(rc, "avc_gemm")
 

@@ -37,6 +37,8 @@ LEDGER = {
     "avc_gemm_bnb_ws": SIZE_QUERY % "avc_gemm_bnb",
     "avc_gemm_set_ring": ["test_gpu_ring.py::test_gelu_epilogues", "test_gpu_ring.py::test_conv_utterance_tile"],
     "avc_gemm_ring_last": ["test_gpu_ring.py::test_conv_utterance_tile"],
+    "avc_gemm_last_path": ["test_gpu_gemm_paths.py::test_gemm_path", "test_gpu_gemm_paths.py::test_refusals_launch_nothing",
+                           "test_abi.py::test_argument_validation_without_gpu"],
     # BatchNorm
     "avc_bn_finalize": [K_ + "test_bn_stats_epilogue_and_finalize", K_ + "test_bn_stats_plain"],
     "avc_bn_eval": [E_ + "test_bn_eval"],

@@ -36,6 +36,22 @@ def rinf(a, b):
     return float((a - b).abs().max() / max(b.abs().max().item(), 1e-30))
 
 
+def _path(family, variant=0, *flags):
+    """The avc_gemm_last_path value of a kernel family / variant / flag bits (autoformer_amd._lib.PATH_*)."""
+    from autoformer_amd import _lib
+
+    from .gemm_path_cases import gemm_path
+
+    return gemm_path(getattr(_lib, "PATH_" + family), variant, sum(getattr(_lib, "PATH_" + f) for f in flags))
+
+
+def _ran(want):
+    from autoformer_amd import kernels as Kr
+
+    got = Kr.gemm_last_path()
+    assert got == want, f"ran on path {got:#x}, expected {want:#x}"
+
+
 def _gemm_ref(A_, B_):  # A (M,K) B (N,K)
     return A_.double() @ B_.double().t()
 
@@ -185,8 +201,9 @@ def test_bn_stats_plain(M, C, ld):
 @pytest.mark.parametrize("comp,nupd", [("bf16", 1), ("bf16", 2), ("fp32", 2)])
 def test_gemm_bn_fused_finalize(M, C, Kd, comp, nupd):
     """avc_gemm_bn: the BN finalize done by the GEMM's last-arriving row tile of each column tile
-    (bf16 fast kernels) or by finalize launches after it (fp32 generic kernel) == the separate
-    avc_bn_finalize on the same partials; running statistics updated nupd times."""
+    (bf16: the operands are fp32-stored, so the 64-wide gemm_fast_kernel at every shape here) or by
+    finalize launches after it (fp32: the generic kernel) == the separate avc_bn_finalize on the same
+    partials; running statistics updated nupd times."""
     import autoformer_amd as A
     from autoformer_amd import kernels as Kr
 
@@ -202,6 +219,7 @@ def test_gemm_bn_fused_finalize(M, C, Kd, comp, nupd):
         rm1, rv1, n1 = rm0.clone(), rv0.clone(), torch.zeros((), dtype=torch.long, device=DEV)
         st1 = Kr.gemm(M, C, Kd, Kr.operand(x, Kd), Kr.operand(w, Kd), y1, bias=bias, bn_partial=p1,
                       bn_fin=(gamma, beta, rm1, rv1, n1, 0.1, 1e-5, nupd))
+        _ran(_path("FAST", 1) if comp == "bf16" else _path("GENERIC"))
         y2 = torch.empty(M, C, device=DEV)
         p2 = Kr.bn_partial_buffer(M, C, DEV)
         rm2, rv2, n2 = rm0.clone(), rv0.clone(), torch.zeros((), dtype=torch.long, device=DEV)
@@ -394,6 +412,9 @@ def test_losses_and_adam():
 
 
 def test_gemm_fast_bf16_copy_and_mixed_dtypes():
+    """The bf16 twin and the four operand-dtype pairs at an aligned NN shape: an fp32-stored operand
+    takes the 64-wide gemm_fast_kernel; the bf16 / bf16 pair runs on the ring (ring / gemm).  Every
+    gemm_fast_kernel instance is covered by test_gpu_gemm_paths.py."""
     import autoformer_amd as A
     from autoformer_amd import kernels as Kr
 
@@ -408,6 +429,7 @@ def test_gemm_fast_bf16_copy_and_mixed_dtypes():
             c = torch.empty(M, N, device=DEV)
             c16 = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
             Kr.gemm(M, N, K_, Kr.operand(ad, K_), Kr.operand(bd, K_), c, c_bf16=c16)
+            _ran(_path("RING", 1) if adt == bdt == torch.bfloat16 else _path("FAST", 1))
             assert relf(c, ref) < 1e-5
             assert relf(c16.float(), ref) < 5e-3
 
@@ -451,9 +473,11 @@ def test_lstm_persistent_forward_matches_per_step(B, H):
 @pytest.mark.parametrize("M,N,K,split", [(300, 200, 96, 1), (1000, 80, 400, 1), (1024, 512, 2560, 1),
                                          (513, 640, 1024, 3), (64, 136, 8, 1)])
 def test_gemm_nt_lds_pipeline_bf16_operands(M, N, K, split):
-    """bf16 K-contiguous operands take the LDS-DMA NT kernel (gemm_nt.hip): products of bf16
-    values accumulate in fp32, so the result matches an fp64 product of the same bf16 values
-    to fp32 accumulation error (M/N tails, K tails of 8, split-K, bias)."""
+    """bf16 K-contiguous operands: products of bf16 values accumulate in fp32, so the result matches an
+    fp64 product of the same bf16 values to fp32 accumulation error (M/N tails, K tails of 8, split-K,
+    bias).  The four split == 1 cases run on the ring (ring / gemm) since it arrived; the split-K case
+    (atomics, which the ring declines) runs the 64-wide tile of the LDS-DMA NT kernel (gemm_nt.hip).
+    gemm_nt.hip's other instances are covered by test_gpu_gemm_paths.py."""
     import autoformer_amd as A
     from autoformer_amd import kernels as Kr
 
@@ -465,6 +489,7 @@ def test_gemm_nt_lds_pipeline_bf16_operands(M, N, K, split):
     c = torch.empty(M, N, device=DEV)
     ad, bd = a.to(DEV), b.to(DEV)
     Kr.gemm(M, N, K, Kr.operand(ad, K), Kr.operand(bd, K), c, bias=bias.to(DEV), split_k=split)
+    _ran(_path("RING", 1) if split == 1 else _path("NT", 1))
     assert relf(c, ref) < 1e-5, relf(c, ref)
 
 
@@ -472,9 +497,11 @@ def test_gemm_nt_lds_pipeline_bf16_operands(M, N, K, split):
                                                  (8, 176, 512, 80, 5, 2), (5, 50, 96, 136, 5, 2), (1, 3, 32, 64, 5, 2)])
 def test_gemm_nt_conv_window_and_bn_stats(B, T, Cin, Cout, Kw, pad):
     """Windowed (im2col) A operand + the BN partial-statistics epilogue.  Five-tap 'same' convs
-    with Cin % 32 == 0 take the halo-reuse conv kernel (gemm_conv.hip): tiles inside one
-    utterance (T=128), tiles spanning utterances (T=37, 50, 176), utterances shorter than the
-    halo (T=3), and output-channel tails (80, 96, 136)."""
+    with Cin % 32 == 0 take the halo-reuse conv kernel (gemm_conv.hip): tiles spanning utterances
+    (T=37, 50, 176), utterances shorter than the halo (T=3), and output-channel tails (80, 96, 136) --
+    except the utterance-aligned (64, 128, 512, 512) case, which meets the halo-ring conditions
+    (T % 128 == 0, Cout >= 128) and runs conv_ring_kernel (ring / halo conv).  The 3-tap case streams
+    its window on the ring (ring / gemm).  gemm_conv.hip on a T = 128 conv: test_gpu_gemm_paths.py."""
     import autoformer_amd as A
     from autoformer_amd import kernels as Kr
 
@@ -489,6 +516,7 @@ def test_gemm_nt_conv_window_and_bn_stats(B, T, Cin, Cout, Kw, pad):
     part = Kr.bn_partial_buffer(M, Cout, DEV)
     Kr.gemm(M, Cout, Kw * Cin, Kr.operand(x.reshape(M, Cin).to(DEV), Cin, window=(Kw, pad, T, T, Cin)),
             Kr.operand(Wf, Kw * Cin), y, bn_partial=part)
+    _ran(_path("RING", 1) if Kw == 3 else _path("RING", 2) if (T % 128 == 0 and Cout >= 128) else _path("CONV"))
     assert relf(y, ref) < 1e-5, relf(y, ref)
     mean, rstd, _, _ = Kr.bn_finalize(part, M, Cout, None, None, None, None, None, 0.1, 1e-5)
     refm = ref.mean(0)
@@ -598,7 +626,8 @@ def _im2col(x, B, T, Cin, Kw, pad):
 @pytest.mark.parametrize("M,N,K,split", [(256, 640, 1000, 1), (80, 1024, 513, 3), (512, 2560, 2048, 2)])
 def test_gemm_tt_lds_transposed_reads(M, N, K, split):
     """K-strided bf16 operands take the LDS-DMA TT kernel (gemm_tt.hip, ds_read_b64_tr_b16
-    fragments); exact products of bf16 values, fp32 accumulation."""
+    fragments; the plain form, its split-K cases reduced through the workspace); exact products of
+    bf16 values, fp32 accumulation."""
     import autoformer_amd as A
     from autoformer_amd import kernels as Kr
 
@@ -609,6 +638,7 @@ def test_gemm_tt_lds_transposed_reads(M, N, K, split):
     c = torch.empty(M, N, device=DEV)
     Kr.gemm(M, N, K, Kr.operand(a.to(DEV), M, kstrided=True), Kr.operand(b.to(DEV), N, kstrided=True), c,
             split_k=split)
+    _ran(_path("TT", 1, *(["SPLITK_WS"] if split > 1 else [])))
     assert relf(c, ref) < 1e-5, relf(c, ref)
 
 
@@ -620,7 +650,8 @@ def test_gemm_tt_conv_weight_gradient_window(B, T, Cin, Cout, Kw, pad, split):
     """Conv dW through the TT kernel.  5-tap 'same' convs with Cin % 32 == 0 take the halo form
     (one x tile for all taps; utterance edges zero-filled at load; K-tiles on the utterance grid,
     the last one of an utterance partial when T % 64 != 0: T = 37, 100, 176), the others the
-    window stream; split-K (atomics) and single-pass (plain stores) epilogues."""
+    window stream (the 3-tap case); split-K (reduced through the workspace: every automatic split here
+    is within the bound of 8) and single-pass (plain stores) epilogues."""
     import autoformer_amd as A
     from autoformer_amd import kernels as Kr
 
@@ -630,9 +661,10 @@ def test_gemm_tt_conv_weight_gradient_window(B, T, Cin, Cout, Kw, pad, split):
     ref = dy.double().t() @ _im2col(x.double(), B, T, Cin, Kw, pad)
     M, N = Cout, Kw * Cin
     c = torch.empty(M, N, device=DEV)
+    sk = Kr.auto_split_k(M, N, B * T) if split == "auto" else split
     Kr.gemm(M, N, B * T, Kr.operand(dy.to(DEV), Cout, kstrided=True),
-            Kr.operand(x.to(DEV), Cin, kstrided=True, window=(Kw, pad, T, T, Cin)), c,
-            split_k=Kr.auto_split_k(M, N, B * T) if split == "auto" else split)
+            Kr.operand(x.to(DEV), Cin, kstrided=True, window=(Kw, pad, T, T, Cin)), c, split_k=sk)
+    _ran(_path("TT", 3 if Kw == 5 else 2, *(["SPLITK_WS"] if Kr.tt_splitk_reduced(sk) else [])))
     assert relf(c, ref) < 1e-5, relf(c, ref)
 
 
@@ -667,6 +699,7 @@ def test_gemm_tt_splitk_reduction_accumulates_and_is_deterministic(kind):
     for split in (5, 5, 7, 1):
         c = base.to(DEV).clone()
         Kr.gemm(M, N, K, opa, opb, c, accumulate=True, split_k=split, cperm=5 if kind == "halo-cperm" else 0)
+        _ran(_path("TT", 1 if kind == "tt" else 3, *(["SPLITK_WS"] if split > 1 else [])))
         torch.cuda.synchronize()
         outs.append(c.cpu())
         assert relf(c - base.to(DEV), ref) < 1e-5, relf(c - base.to(DEV), ref)
@@ -674,7 +707,8 @@ def test_gemm_tt_splitk_reduction_accumulates_and_is_deterministic(kind):
 
 
 def test_gemm_tt_time_shift_window():
-    """dW_hh = dG^T . h_{t-1}: B operand is h shifted one frame inside each utterance."""
+    """dW_hh = dG^T . h_{t-1}: B operand is h shifted one frame inside each utterance (gemm_tt.hip's
+    window stream)."""
     import autoformer_amd as A
     from autoformer_amd import kernels as Kr
 
@@ -689,6 +723,7 @@ def test_gemm_tt_time_shift_window():
     c = torch.empty(G, H, device=DEV)
     Kr.gemm(G, H, B * T, Kr.operand(dg.to(DEV), G, kstrided=True),
             Kr.operand(h.to(DEV), H, kstrided=True, window=(1, 1, T, T, H)), c)
+    _ran(_path("TT", 2))
     assert relf(c, ref) < 1e-5, relf(c, ref)
 
 
@@ -868,7 +903,9 @@ def test_lstm2_wavefront_autograd_matches_layerwise():
 def test_gemm_bnb_matches_separate_bn_backward(out_bf16, act_name):
     """avc_gemm_bnb (the producing layer's BatchNorm backward statistics in the GEMM epilogue,
     last-row-tile finalize) + avc_bn_bwd_apply equal avc_bn_bwd's reduce / finalize / apply
-    passes over the same GEMM output: dy, dgamma, dbeta and the conv-bias gradient."""
+    passes over the same GEMM output: dy, dgamma, dbeta and the conv-bias gradient.  The plain
+    product runs on the ring; avc_gemm_bnb on the 64-wide BN-backward instance of gemm_nt.hip (the
+    ring has that epilogue on its halo conv only)."""
     import autoformer_amd as A
     from autoformer_amd import kernels as Kr
 
@@ -886,12 +923,14 @@ def test_gemm_bnb_matches_separate_bn_backward(out_bf16, act_name):
     dt = torch.bfloat16 if out_bf16 else torch.float32
     c_ref = torch.empty(M, N, device=DEV, dtype=dt)
     Kr.gemm(M, N, Kd, Kr.operand(a, Kd), Kr.operand(w, Kd), c_ref)
+    _ran(_path("RING", 1))
     dy_ref, dg_ref, db_ref, dbi_ref = Kr.bn_bwd(c_ref, None, y, mean, rstd, gamma, act, beta=beta)
     c = torch.empty(M, N, device=DEV, dtype=dt)
     coef = torch.empty(6 * N, device=DEV)
     dg, db, dbi = (torch.full((N,), 0.25, device=DEV) for _ in range(3))  # accumulate onto 0.25
     Kr.gemm(M, N, Kd, Kr.operand(a, Kd), Kr.operand(w, Kd), c,
             bnb=(y, mean, rstd, gamma, beta, act, coef, dg, db, dbi, 1))
+    _ran(_path("NT", 1, "BNB"))
     dy = Kr.bn_bwd_apply(c, y, coef, act)
     torch.cuda.synchronize()
     torch.testing.assert_close(c, c_ref, rtol=0, atol=0)
@@ -1125,8 +1164,10 @@ def Kr_act_relu():
 def test_conv_bn_fused_finalize(B, T, Cin, Cout):
     """The halo conv kernels with the BN finalize in their epilogue (the forward conv + BN of every
     ConvNorm layer) against the same conv with the separate finalize: y, partials, mean / rstd /
-    scale / shift and the running statistics.  Utterance-aligned shapes (T % 128 == 0) take the
-    eight-wave ring kernel (gemm_ring.hip conv_ring_kernel), the others gemm_conv.hip."""
+    scale / shift and the running statistics.  The utterance-aligned shape with Cout >= 128
+    ((64, 128, 512, 512)) takes the eight-wave ring kernel (gemm_ring.hip conv_ring_kernel: ring / halo
+    conv), the others gemm_conv.hip -- (8, 176, 512, 80) and (2, 300, 32, 64) too: Cout < 128 keeps
+    them off the ring and off its one-utterance tile."""
     import autoformer_amd as A
     from autoformer_amd import kernels as Kr
 
@@ -1147,8 +1188,10 @@ def test_conv_bn_fused_finalize(B, T, Cin, Cout):
         if fused:
             st = Kr.gemm(M, Cout, 5 * Cin, xo, wo, y, bias=bias, bn_partial=p,
                          bn_fin=(gamma, beta, rm, rv, n, 0.1, 1e-5, 1))
+            _ran(_path("RING", 2) if (T % 128 == 0 and Cout >= 128) else _path("CONV"))
         else:
             Kr.gemm(M, Cout, 5 * Cin, xo, wo, y, bias=bias, bn_partial=p)
+            _ran(_path("RING", 2) if (T % 128 == 0 and Cout >= 128) else _path("CONV"))
             st = Kr.bn_finalize(p, M, Cout, gamma, beta, rm, rv, n, 0.1, 1e-5)
         torch.cuda.synchronize()
         outs.append((y, p, st, rm, rv))

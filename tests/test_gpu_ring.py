@@ -13,6 +13,8 @@ Operands are bf16 (exact in fp32), so the references are fp32 products of the sa
 import pytest
 import torch
 
+from .helpers import report, sum_ratio
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
@@ -32,18 +34,39 @@ def _bf16_and_reset():
     _ring(-1)
 
 
+def _path():
+    """avc_gemm_last_path of the last K.gemm on this thread."""
+    from autoformer_amd import kernels as K
+
+    return K.gemm_last_path()
+
+
+def _p(family, variant=0, flags=0):
+    from autoformer_amd import _lib
+
+    from .gemm_path_cases import gemm_path
+
+    return gemm_path(getattr(_lib, "PATH_" + family), variant, getattr(_lib, "PATH_" + flags) if flags else 0)
+
+
 def _rel(a, b):
     return ((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30)).item()
 
 
 CFGS = [(256, 256, 2), (256, 128, 3), (128, 128, 4), (128, 128, 3), (128, 256, 3), (256, 128, 2),
-        (256, 256, 14), (256, 128, 15), (128, 128, 16), (128, 128, 2)]  # nst 10 + n: 32-deep slots (gemm_ring32_kernel)
+        (256, 256, 14), (256, 128, 15), (128, 128, 16), (128, 128, 2)]
+# nst 14 / 15 / 16 named the 32-deep-slot ring (nst 10 + n), which is gone: gemm_ring_launch_ has no such
+# configuration and declines it, so those three rows run the 64-wide gemm_nt.hip tile (the witness below)
 
 
 @pytest.mark.parametrize("cfg", CFGS)
 @pytest.mark.parametrize("M,N,Kd", [(1000, 300, 200), (513, 1100, 72), (256, 256, 64)])
 def test_ring_gemm_configs(cfg, M, N, Kd):
+    """gemm_ring_kernel at every forced tile configuration it is instantiated for (ring / gemm); the
+    three nst >= 10 rows are declined by the ring and run gemm_nt.hip's 64-wide tile."""
     from autoformer_amd import kernels as K
+
+    want = _p("RING", 1) if cfg[2] < 10 else _p("NT", 1)
 
     torch.manual_seed(M + N + Kd)
     a = torch.randn(M, Kd, device=DEV).bfloat16()
@@ -55,19 +78,31 @@ def test_ring_gemm_configs(cfg, M, N, Kd):
     c = torch.empty(M, N, device=DEV)
     c16 = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
     K.gemm(M, N, Kd, K.operand(a, Kd), K.operand(b, Kd), c, bias=bias, residual=res, c_bf16=c16)
+    assert _path() == want, hex(_path())
     torch.cuda.synchronize()
     assert _rel(c, ref) < 1e-5
+    # per element against float64 (bf16-exact operands: only the fp32 accumulation errs): the any-order
+    # summation bound over K products plus the epilogue's additions, as in test_gpu_gemm_paths.py
+    prod64 = a.double() @ b.double().t()
+    S = a.double().abs() @ b.double().abs().t()
+    assert report("ring", f"configs {cfg} {M}x{N}x{Kd} C",
+                  sum_ratio(c, (prod64 + bias.double() + res.double()).cpu(),
+                            (S + bias.double().abs() + res.double().abs()).cpu(), Kd + 5)) <= 1
     assert _rel(c16.float(), ref) < 1e-2
     # bf16-only output (the 16-B bf16 store path of the ring epilogue), no residual
     o16 = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
     K.gemm(M, N, Kd, K.operand(a, Kd), K.operand(b, Kd), o16, bias=bias)
+    assert _path() == want, hex(_path())
     torch.cuda.synchronize()
     assert _rel(o16.float(), ref - res) < 1e-2
     # accumulate on top
     c2 = c.clone()
     K.gemm(M, N, Kd, K.operand(a, Kd), K.operand(b, Kd), c2, accumulate=True)
+    assert _path() == want, hex(_path())
     torch.cuda.synchronize()
     assert _rel(c2, c + a.float() @ b.float().t()) < 1e-5
+    assert report("ring", f"configs {cfg} {M}x{N}x{Kd} accumulate",
+                  sum_ratio(c2, (c.double() + prod64).cpu(), (c.double().abs() + S).cpu(), Kd + 5)) <= 1
 
 
 def test_ring_default_policy_and_batch_fold():
@@ -83,6 +118,7 @@ def test_ring_default_policy_and_batch_fold():
     c = torch.empty(B * D, N4, device=DEV)
     K.gemm(D, N4, NPp, K.operand(a, NPp, batch_stride=D * NPp), K.operand(w, NPp), c, bias=bias, batch=B,
            c_batch_stride=D * N4)
+    assert _path() == _p("RING", 1), hex(_path())
     torch.cuda.synchronize()
     assert _rel(c, a.float() @ w.float().t() + bias) < 1e-5
 
@@ -91,6 +127,8 @@ def test_ring_default_policy_and_batch_fold():
                                                   (3, 176, 96, 200, True), (2, 50, 32, 64, True)])
 @pytest.mark.parametrize("bn", [False, True])
 def test_conv_ring(B, T, Cin, Cout, forced, bn):
+    """conv_ring_kernel (ring / halo conv: the default policy on utterance-aligned tiles, forced on
+    straddling ones) and, with the ring off, gemm_conv.hip on the same conv."""
     from autoformer_amd import kernels as K
 
     torch.manual_seed(B * T + Cin)
@@ -116,6 +154,7 @@ def test_conv_ring(B, T, Cin, Cout, forced, bn):
         else:
             st = None
             K.gemm(M, Cout, 5 * Cin, xo, wo, y, bias=bias)
+        assert _path() == (_p("CONV") if mode == (0,) else _p("RING", 2)), (mode, hex(_path()))
         torch.cuda.synchronize()
         outs.append((y, st))
         assert _rel(y, ref) < 1e-5, mode
@@ -153,6 +192,7 @@ def test_conv_utterance_tile(B, T, Cin, Cout, bn):
     else:
         K.gemm(M, Cout, 5 * Cin, xo, wo, y, bias=bias)
     assert _lib.lib().avc_gemm_ring_last() == 3, "the one-utterance halo conv did not run"
+    assert _path() == _p("RING", 3), hex(_path())
     y16 = torch.empty(M, Cout, device=DEV, dtype=torch.bfloat16)
     K.gemm(M, Cout, 5 * Cin, xo, wo, y16, bias=bias)  # bf16-only output (the 16-B store path)
     torch.cuda.synchronize()
@@ -177,8 +217,8 @@ def _gelu_grad(x):
 @pytest.mark.parametrize("ring", [-1, 0])
 @pytest.mark.parametrize("store", ["f32", "bf16"])
 def test_gelu_epilogues(ring, store):
-    """c_bf16_act = GELU and act_grad_of on the ring kernel (-1: N >= 1024) and on the pass after
-    the older kernels (0); store = bf16: the pre-activation goes out in bf16 only (c_pre_bf16), the
+    """c_bf16_act = GELU and act_grad_of on the ring kernel (-1: ring / gemm) and on the pass after
+    the older kernels (0: gemm_nt.hip's 64-wide tile + the GELU pass, PATH_POST_PASS); store = bf16: the pre-activation goes out in bf16 only (c_pre_bf16), the
     backward reads it (act_grad_dtype bf16) and writes its gradient in bf16 only."""
     from autoformer_amd import kernels as K
 
@@ -194,10 +234,13 @@ def test_gelu_epilogues(ring, store):
     _ring(ring)
     u = torch.empty(M, N, device=DEV, dtype=dt)
     v = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
+    want = _p("RING", 1) if ring == -1 else _p("NT", 1, "POST_PASS")
     K.gemm(M, N, Kd, K.operand(a, Kd), K.operand(b, Kd), u, bias=bias, c_bf16=v, c_bf16_act=K.ACT_GELU)
+    assert _path() == want, hex(_path())
     d = torch.empty(M, N, device=DEV, dtype=dt)
     d16 = torch.empty(M, N, device=DEV, dtype=torch.bfloat16) if store == "f32" else None
     K.gemm(M, N, Kd, K.operand(a, Kd), K.operand(b, Kd), d, c_bf16=d16, act_grad_of=x)
+    assert _path() == want, hex(_path())
     torch.cuda.synchronize()
     uref = a.float() @ b.float().t() + bias
     dref = (a.float() @ b.float().t()).double() * _gelu_grad(x)
@@ -237,6 +280,8 @@ def test_col_sum_epilogue(ring, batch, store):
     cs0 = cs.clone()
     K.gemm(M, N, Kd, K.operand(a, Kd, batch_stride=M * Kd), K.operand(b, Kd), d, c_bf16=d16, act_grad_of=x,
            batch=batch, c_batch_stride=M * N, col_sum=cs, col_sum_n=n)
+    # ring / gemm with the sums in its epilogue; ring off: gemm_nt.hip's 64-wide tile, then the GELU' and col_sum pass
+    assert _path() == (_p("RING", 1) if ring == -1 else _p("NT", 1, "POST_PASS")), hex(_path())
     torch.cuda.synchronize()
     dref = (a.float() @ b.float().t()).double() * _gelu_grad(x)
     tol = 1e-5 if store == "f32" else 5e-3
@@ -268,6 +313,8 @@ def test_transposed_store(ring, B, D, NP, Kd):
     z1 = torch.empty(B * NP, D, device=DEV)
     K.gemm(D, NP, Kd, K.operand(v, Kd, batch_stride=D * Kd), K.operand(w, Kd), z1, bias=bias, batch=B,
            c_batch_stride=D * NP, residual=z, c_trans_rows=D)
+    # ring / gemm, or gemm_nt.hip's 64-wide tile through fast_epilogue's out_off (no pass after it)
+    assert _path() == (_p("RING", 1) if ring == -1 else _p("NT", 1)), hex(_path())
     torch.cuda.synchronize()
     rt = (v.float() @ w.float().t() + bias).view(B, D, NP)
     ref = z + rt.transpose(1, 2).reshape(B * NP, D)
@@ -289,6 +336,7 @@ def test_generic_gemm_fused_gelu_outputs():
     u = torch.empty(M, N, device=DEV)
     v = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
     K.gemm(M, N, Kd, K.operand(abuf, Kd + 1), K.operand(b, Kd), u, c_bf16=v, c_bf16_act=K.ACT_GELU)
+    assert _path() == _p("GENERIC", 0, "POST_PASS"), hex(_path())
     torch.cuda.synchronize()
     ref = abuf[:, :Kd].float() @ b.float().t()
     assert _rel(u, ref) < 1e-5
@@ -302,5 +350,6 @@ def test_generic_gemm_fused_gelu_outputs():
     d = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
     with pytest.raises(RuntimeError, match="bf16-only output"):
         K.gemm(M, N, Kd, K.operand(abuf, Kd + 1), K.operand(b, Kd), d, act_grad_of=x)
+    assert _path() == 0  # a refused call launched nothing
     torch.cuda.synchronize()
     assert _lib.lib().avc_abi_version() == _lib.ABI_VERSION
