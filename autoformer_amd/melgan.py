@@ -20,6 +20,10 @@ never runs those submodules: it runs frame-major HIP kernels (melgan.hip + avc_g
 Weight norm (g v / ||v||) is folded into the packed GEMM operands once per parameter version
 (inference weights do not change between calls).  There is no CPU or torch fallback: the
 kernels raise on host tensors.
+
+The other direction, waveform -> log-mel (reference modules.py:26-69 `Audio2Mel`, interface.py:33-41
+`MelVocoder.__call__`), is `Audio2Mel` below: one fused fp32 kernel (audio.hip) behind the
+reference's constructor and buffers, with the Slaney filterbank as a closed form.
 """
 from __future__ import annotations
 
@@ -218,14 +222,183 @@ class Generator(nn.Module):
         return self.frames(xf, B, T).unsqueeze(1)
 
 
+# ----------------------------------------------------------------------------- audio -> mel
+N_FFT, HOP, N_BINS = 1024, 256, 513
+PAD = (N_FFT - HOP) // 2  # reflect padding on either side (modules.py:55)
+CLAMP = 1e-5  # modules.py:68
+
+
+def hz_to_mel(f):
+    """Slaney's mel scale (librosa's htk=False) in fp64: 200/3 Hz per mel below 1 kHz, then
+    ln(6.4)/27 per mel in log frequency."""
+    f = np.asarray(f, dtype=np.float64)
+    lin = f * 3.0 / 200.0
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) / (np.log(6.4) / 27.0), lin)
+
+
+def mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), m * 200.0 / 3.0)
+
+
+def slaney_mel_basis(sr, n_fft, n_mels, fmin=0.0, fmax=None):
+    """The (n_mels, n_fft//2 + 1) fp32 filterbank the reference takes from librosa
+    (htk=False, norm="slaney"), as a closed form in fp64: triangles between n_mels + 2 points equally
+    spaced on the Slaney mel scale, each scaled by 2 / (f[m+2] - f[m]); cast to fp32 at the end."""
+    fmax = sr / 2.0 if fmax is None else float(fmax)
+    bins = np.linspace(0.0, sr / 2.0, n_fft // 2 + 1)
+    f = mel_to_hz(np.linspace(hz_to_mel(fmin), hz_to_mel(fmax), n_mels + 2))
+    ramps = f[:, None] - bins[None, :]
+    fd = np.diff(f)
+    lower = -ramps[:-2] / fd[:-1, None]
+    upper = ramps[2:] / fd[1:, None]
+    w = np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (f[2:] - f[:-2]))[:, None]
+    return w.astype(np.float32)
+
+
+def n_frames(L):
+    """Frames of an L-sample utterance: (L + 2*384 - 1024) // 256 + 1; L <= 384 is refused (the
+    reflection needs pad < length)."""
+    L = int(L)
+    if L <= PAD:
+        raise ValueError(f"Audio2Mel: an utterance of {L} samples is too short: the reflect padding of {PAD} "
+                         f"needs at least {PAD + 1}")
+    return (L + 2 * PAD - N_FFT) // HOP + 1
+
+
+def compact_basis(basis):
+    """(table int32 [n_mel][3] = start, count, offset; weights fp32) of a (n_mel, 513) basis: each
+    filter's span from its first to its last non-zero bin, spans laid end to end."""
+    basis = np.asarray(basis, dtype=np.float32)
+    table = np.zeros((basis.shape[0], 3), dtype=np.int32)
+    chunks, off = [], 0
+    for m, row in enumerate(basis):
+        nz = np.flatnonzero(row)
+        if nz.size:
+            st, cnt = int(nz[0]), int(nz[-1] - nz[0] + 1)
+            table[m] = (st, cnt, off)
+            chunks.append(row[st:st + cnt])
+            off += cnt
+        else:
+            table[m] = (0, 0, off)
+    weights = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.float32)
+    if weights.size == 0:
+        weights = np.zeros(1, dtype=np.float32)
+    return table, weights
+
+
+class Audio2Mel(nn.Module):
+    """modules.py:26-69 with the reference's constructor and its two buffers (`mel_basis`, `window`);
+    the whole chain -- reflect pad, STFT, magnitude, mel, log10 of the clamp -- is one HIP kernel
+    (audio.hip).  The kernel reads the filterbank from the `mel_basis` BUFFER (compacted on the host,
+    cached per buffer version), so a loaded state_dict's basis is the one applied.
+
+      forward(audio (B, 1, L))                      -> (B, n_mel, T)      the reference's contract
+      frames(audio (B, L) or list, lens, scale)     -> (B, Tmax, n_mel)   frame-major, per-utterance
+                                                       lengths, frames past an utterance's end 0.0
+    """
+
+    def __init__(self, n_fft=1024, hop_length=256, win_length=1024, sampling_rate=22050, n_mel_channels=80,
+                 mel_fmin=0.0, mel_fmax=None):
+        super().__init__()
+        if (n_fft, hop_length, win_length) != (N_FFT, HOP, N_FFT):
+            raise ValueError(f"Audio2Mel: n_fft={n_fft} hop_length={hop_length} win_length={win_length}: the kernel "
+                             f"is built for n_fft = win_length = {N_FFT}, hop_length = {HOP} (the reference's values)")
+        if not 1 <= n_mel_channels <= 128:
+            raise ValueError(f"Audio2Mel: n_mel_channels = {n_mel_channels} outside 1..128")
+        window = torch.hann_window(win_length).float()
+        mel_basis = torch.from_numpy(slaney_mel_basis(sampling_rate, n_fft, n_mel_channels, mel_fmin, mel_fmax))
+        self.register_buffer("mel_basis", mel_basis)
+        self.register_buffer("window", window)
+        self.n_fft, self.hop_length, self.win_length = n_fft, hop_length, win_length
+        self.sampling_rate, self.n_mel_channels = sampling_rate, n_mel_channels
+        self._tables = None
+        self._table_key = None
+        self._lens = None
+
+    n_frames = staticmethod(n_frames)
+
+    def tables(self):
+        """(host table, device table, device weights, n_weights, device twiddles) for the current buffers."""
+        mb, win = self.mel_basis, self.window
+        key = (mb.data_ptr(), mb._version, win.data_ptr(), win._version, str(mb.device))
+        if self._tables is None or self._table_key != key:
+            if tuple(mb.shape) != (self.n_mel_channels, N_BINS) or tuple(win.shape) != (N_FFT,):
+                raise ValueError(f"Audio2Mel: mel_basis {tuple(mb.shape)} / window {tuple(win.shape)}, expected "
+                                 f"({self.n_mel_channels}, {N_BINS}) / ({N_FFT},)")
+            table, weights = compact_basis(mb.detach().float().cpu().numpy())
+            if weights.size > L.MEL_MAX_WEIGHTS:
+                raise ValueError(f"Audio2Mel: the compact form of mel_basis has {weights.size} weights; at most "
+                                 f"{L.MEL_MAX_WEIGHTS} fit the kernel's LDS budget")
+            ang = 2.0 * np.pi * np.arange(N_BINS, dtype=np.float64) / N_FFT
+            tw = np.stack((np.cos(ang), -np.sin(ang)), axis=1).astype(np.float32)
+            host = (L.c_int * table.size)(*[int(v) for v in table.reshape(-1)])
+            dev = mb.device
+            self._tables = (host, torch.from_numpy(table.reshape(-1).copy()).to(dev), torch.from_numpy(weights).to(dev),
+                            int(weights.size), torch.from_numpy(tw).to(dev))
+            self._table_key = key
+        return self._tables
+
+    @torch.no_grad()
+    def _run(self, audio, lens, scale, layout):
+        K._dev(audio, self.mel_basis, self.window, scale)
+        if audio.dim() != 2 or audio.dtype != torch.float32:
+            raise ValueError(f"Audio2Mel: expected fp32 audio (B, L), got {tuple(audio.shape)} {audio.dtype}")
+        audio = audio.contiguous()
+        B, stride = audio.shape
+        lens = [stride] * B if lens is None else [int(v) for v in lens]
+        if len(lens) != B:
+            raise ValueError(f"Audio2Mel: lens must hold B={B} values")
+        if max(lens) > stride:
+            raise ValueError(f"Audio2Mel: lens {max(lens)} exceeds the {stride} samples of a row")
+        Tmax = max(n_frames(v) for v in lens)
+        if scale is not None:
+            scale = scale.to(device=audio.device, dtype=torch.float32).contiguous()
+            if scale.shape != (B,):
+                raise ValueError(f"Audio2Mel: scale must hold B={B} values")
+        host, tab, wts, nw, tw = self.tables()
+        n_mel = self.n_mel_channels
+        win = self.window if self.window.dtype == torch.float32 else self.window.float()
+        lkey = (tuple(lens), str(audio.device))
+        if self._lens is None or self._lens[0] != lkey:  # the same lengths again: no second upload
+            self._lens = (lkey, (L.c_int * B)(*lens), torch.tensor(lens, dtype=torch.int32, device=audio.device))
+        _, lens_host, lens_dev = self._lens
+        shape = (B, Tmax, n_mel) if layout == L.MEL_FRAME_MAJOR else (B, n_mel, Tmax)
+        out = torch.empty(shape, device=audio.device)
+        L.call("avc_audio2mel", audio.data_ptr(), stride, lens_host, lens_dev.data_ptr(), K._ptr(scale), B,
+               win.contiguous().data_ptr(), tw.data_ptr(), host, tab.data_ptr(), wts.data_ptr(), nw, n_mel, N_FFT,
+               N_FFT, HOP, CLAMP, out.data_ptr(), Tmax, layout, K.stream())
+        return out
+
+    def frames(self, audio, lens=None, scale=None):
+        """audio: (B, L) fp32 on the device, rows valid up to lens[b] (default L), or a list of 1-D
+        tensors of any lengths.  scale: (B,) device factors applied to the samples (the magnitude is
+        linear in them).  -> (B, Tmax, n_mel) frame-major log-mel, 0.0 in frames t >= T_b."""
+        if isinstance(audio, (list, tuple)):
+            if lens is not None:
+                raise ValueError("Audio2Mel.frames: a list of utterances carries its own lengths")
+            lens = [int(a.numel()) for a in audio]
+            buf = torch.zeros(len(audio), max(lens), device=self.mel_basis.device)
+            for b, a in enumerate(audio):
+                buf[b, :lens[b]] = a.reshape(-1)
+            audio = buf
+        return self._run(audio, lens, scale, L.MEL_FRAME_MAJOR)
+
+    def forward(self, audio):
+        """audio (B, 1, L) -> log-mel (B, n_mel, T) (modules.py:54-69)."""
+        if audio.dim() != 3 or audio.shape[1] != 1:
+            raise ValueError(f"Audio2Mel.forward: expected audio (B, 1, L), got {tuple(audio.shape)}")
+        return self._run(audio.float().squeeze(1), None, None, L.MEL_CHANNEL_MAJOR)
+
+
 class MelVocoder:
-    """melgan/interface.py:23-53: `inverse(mel (B, 80, T)) -> (B, T*256)` on the HIP generator.
-    The checkpoint is read with torch.load(weights_only=True).  `__call__` (audio -> mel,
-    Audio2Mel: librosa's Slaney filterbank + STFT, modules.py:26-69) is not part of the
-    conversion path (evaluate.py only calls `inverse`) and is not restated."""
+    """melgan/interface.py:23-53: `inverse(mel (B, 80, T)) -> (B, T*256)` on the HIP generator and
+    `__call__(audio (B, L)) -> (B, 80, T)` on the HIP Audio2Mel.  The checkpoint is read with
+    torch.load(weights_only=True)."""
 
     def __init__(self, device="cuda:0", model_name="multi_speaker", generator=None):
         self.device = torch.device(device)
+        self.fft = Audio2Mel().to(self.device)
         if generator is None:
             generator = Generator(80, 32, 3)
             sd = torch.load(f"{model_name}.pt", map_location="cpu", weights_only=True)
@@ -233,8 +406,8 @@ class MelVocoder:
         self.mel2wav = generator.to(self.device)
 
     def __call__(self, audio):
-        raise NotImplementedError("MelVocoder.__call__ (Audio2Mel, librosa filterbank) is not on the conversion "
-                                  "path and is not restated (autoformer_amd/melgan.py)")
+        """audio (B, L) -> log-mel (B, 80, T) (interface.py:33-41)."""
+        return self.fft(audio.unsqueeze(1).to(self.device))
 
     def inverse(self, mel):
         return self.mel2wav(mel.to(self.device)).squeeze(1)

@@ -1,1 +1,1 @@
-from autoformer_amd.melgan import Generator, ResnetBlock, WNConv1d, WNConvTranspose1d  # noqa: F401
+from autoformer_amd.melgan import Audio2Mel, Generator, ResnetBlock, WNConv1d, WNConvTranspose1d  # noqa: F401
