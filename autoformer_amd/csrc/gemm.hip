@@ -600,9 +600,7 @@ __global__ void __launch_bounds__(256, 2) gemm_fast_kernel(GemmArgs g) {
   const int wm = wid >> 1, wn = wid & 1;
 
   // XCD-aware bijective remap: blocks that share an A row-panel run on one XCD's L2.
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7;
-  const int lid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int nN = (g.N + BN_ - 1) / BN_, nM = (g.M + BM - 1) / BM;
   const int z = lid / (nN * nM);
   const int rem = lid - z * nN * nM;

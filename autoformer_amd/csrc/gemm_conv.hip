@@ -18,7 +18,7 @@
 //
 // 128 x 64 tile, 4 waves (2 x 2, each 64 x 32), 16x16x32 bf16 MFMA, two LDS stages of 32 KiB
 // so two workgroups share a CU (measured on the AutoVC convs: 33 us per 8192x512x2560 conv vs
-// 50 us with four stages at one workgroup per CU, 40 us for the window stream), global_load_lds_dwordx4 (16 B per lane, no register staging) into
+// 50 us with four stages at one workgroup per CU, 40 us for the window stream), LDS-DMA fills (glds16: 16 B per lane, no register staging) into
 // 64-B rows XOR-swizzled by 16-B chunk (chunk ^ ((row >> 1) & 3), applied on the source
 // address), counted vmcnt + raw barrier, shared fused epilogue (gemm_internal.h: bias, BN
 // partial statistics, bf16 twin, accumulate, residual).
@@ -26,20 +26,6 @@
 
 namespace avcg {
 namespace {
-
-__device__ __attribute__((aligned(16))) unsigned int g_zero16_cv[4] = {0u, 0u, 0u, 0u};
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-__device__ __forceinline__ void glds16(const void* src, char* lds) {
-  __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)lds, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void raw_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 // CBK channels per stage (LDS rows of 2*CBK bytes), CBN output columns per tile, 128-row tiles,
 // 4 waves (2 along M, 2 along N).  Every wave issues the same number of glds per
@@ -78,9 +64,7 @@ __global__ void __launch_bounds__(256, 2) gemm_conv_kernel(GemmArgs g) {
   const int wm = wid >> 1, wn = wid & 1;
 
   // XCD-aware bijective remap (as gemm_nt_kernel)
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7;
-  const int lid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int nN = (g.N + CBN - 1) / CBN;
   const int mt = lid / nN, nt = lid - mt * nN;
   const int m0 = mt * TM, n0 = nt * CBN;
@@ -118,10 +102,10 @@ __global__ void __launch_bounds__(256, 2) gemm_conv_kernel(GemmArgs g) {
     const int c0 = cs * CBK;
 #pragma unroll
     for (int i = 0; i < AI4; ++i)
-      glds16(aok[i] ? (const void*)(xa + aoff[i] + c0) : (const void*)g_zero16_cv, base + (AI4 * wid + i) * 1024);
+      glds16(aok[i] ? (const void*)(xa + aoff[i] + c0) : (const void*)g_zero16, base + (AI4 * wid + i) * 1024);
 #pragma unroll
     for (int i = 0; i < BI4; ++i)
-      glds16(bok[i] ? (const void*)(wb + boff[i] + c0) : (const void*)g_zero16_cv,
+      glds16(bok[i] ? (const void*)(wb + boff[i] + c0) : (const void*)g_zero16,
              base + C::A_BYTES + (wid * BI4 + i) * 1024);
   };
 
@@ -156,17 +140,7 @@ __global__ void __launch_bounds__(256, 2) gemm_conv_kernel(GemmArgs g) {
     if (p < nst) issue(p, p);
 
   for (int cs = 0; cs < nst; ++cs) {
-    const int ahead = min(P - 1, nst - 1 - cs);
-    if constexpr (P >= 3) {
-      if (ahead >= 2) wait_vm<2 * LPT>();
-      else if (ahead == 1) wait_vm<LPT>();
-      else wait_vm<0>();
-    } else if constexpr (P == 2) {
-      if (ahead >= 1) wait_vm<LPT>();
-      else wait_vm<0>();
-    } else {
-      wait_vm<0>();
-    }
+    ring_wait<P, LPT>(min(P - 1, nst - 1 - cs));
     raw_barrier();
     if (cs + P < nst) issue((cs + P) % NST, cs + P);
     const char* st = smem_raw + (cs % NST) * STAGE;
@@ -243,7 +217,7 @@ bool gemm_conv_launch(const GemmArgs& g, hipStream_t s) {
   }
   // (round 3 measured 256-row tiles of this kernel -- eight waves, one workgroup per CU, three
   // 48-KiB stages -- no faster, profiles/r3_conv_tile_ab.txt; round 4 removed that form: the
-  // eight-wave halo conv is gemm_ring.hip's conv_ring_kernel)
+  // eight-wave halo conv is conv_ring.hip's conv_ring_kernel)
 #define CONV_CASE(NS, BK, BN)                  \
   if (ns == NS && bk == BK && bn == BN) {      \
     launch<NS, BK, BN>(g, s);                  \

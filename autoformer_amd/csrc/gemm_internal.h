@@ -1,5 +1,6 @@
-// gemm_internal.h — device-side GEMM argument structs and the shared MFMA epilogue used by
-// the LDS-tiled kernels in gemm.hip and gemm_nt.hip (internal to libautovc_hip.so).
+// gemm_internal.h — device-side GEMM argument structs, the XCD block remap, the LDS-DMA helpers of
+// the pipelined kernels and the shared MFMA epilogue of the four-wave kernels in gemm.hip, gemm_nt.hip,
+// gemm_conv.hip and gemm_tt.hip (internal to libautovc_hip.so).
 #pragma once
 #include "common.h"
 #include "bn_internal.h"
@@ -10,6 +11,49 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128;                    // rows per workgroup tile (BN partial-stat tiles follow it)
 constexpr int FBK = 64;                    // K per LDS stage of the fast kernels
+
+// XCD-aware bijective block remap: the hardware deals blocks b, b + 8, ... to one XCD, so block
+// `bid` of `nwg` gets the linear id that puts each XCD on a contiguous run of ids (the blocks an
+// XCD runs together then share operand panels in its L2).  The tile order on top of the returned
+// id is each kernel's own.
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7;
+  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+}
+
+// ---- LDS-DMA helpers of the pipelined kernels (gemm_nt / gemm_conv / gemm_tt / gemm_ring / conv_ring)
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
+
+// source of padding rows and tails: a fill reads these 16 zero bytes instead of branching.  One per
+// translation unit (internal linkage: the library is built without relocatable device code)
+static __device__ __attribute__((aligned(16), unused)) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
+
+// one 16-B-per-lane global -> LDS fill (no register staging)
+__device__ __forceinline__ void glds16(const void* src, char* lds) {
+  __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)lds, 16, 0, 0);
+}
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+__device__ __forceinline__ void raw_barrier() { asm volatile("s_barrier" ::: "memory"); }
+
+// Counted wait in front of a ring step: P steps of fills are issued ahead, LPT per thread each, and
+// `ahead` of them (those after the step about to be read, <= P - 1) may stay in flight.
+template <int P, int LPT>
+__device__ __forceinline__ void ring_wait(int ahead) {
+  if constexpr (P >= 3) {
+    if (ahead >= 2) wait_vm<2 * LPT>();
+    else if (ahead == 1) wait_vm<LPT>();
+    else wait_vm<0>();
+  } else if constexpr (P == 2) {
+    if (ahead >= 1) wait_vm<LPT>();
+    else wait_vm<0>();
+  } else {
+    wait_vm<0>();
+  }
+}
 
 struct OpDev {
   const void* ptr;

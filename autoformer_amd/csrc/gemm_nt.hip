@@ -7,8 +7,8 @@
 // AutoVC.py:43,77,96) once their operands are bf16.
 //
 // Structure (cdna_hip_programming.md §5): 128 x BN_ tile, BK = 64, 4 waves as 2x2, each wave
-// 64 x BN_/2 of 16x16x32 MFMAs.  Operands go global -> LDS with global_load_lds_dwordx4
-// (16 B per lane, no register staging), NST LDS stages, NST-1 tiles in flight: a counted
+// 64 x BN_/2 of 16x16x32 MFMAs.  Operands go global -> LDS by LDS DMA (glds16:
+// 16 B per lane, no register staging), NST LDS stages, NST-1 tiles in flight: a counted
 // `s_waitcnt vmcnt` + raw s_barrier per K-tile, never vmcnt(0) inside the loop.  LDS rows
 // are 128 B, XOR-swizzled by 16-B chunk (chunk ^= (row >> 1) & 7) on the SOURCE address so
 // the ds_read_b128 fragment reads are bank-conflict free.  Padding / tails read a 16-B
@@ -18,22 +18,7 @@
 namespace avcg {
 namespace {
 
-__device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-
 constexpr int ROWB = FBK * 2;  // 128-byte LDS rows
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
-
-__device__ __forceinline__ void glds16(const void* src, char* lds) {
-  __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)lds, 16, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void raw_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 // One operand's tile loader: R rows x 64 K per stage = R/32 glds per thread.  Instruction i
 // of wave w covers tile rows (4i + w)*8 .. +8; lane L writes row +(L>>3), 16-B slot L&7,
@@ -112,9 +97,7 @@ __global__ void __launch_bounds__(256, 1) gemm_nt_kernel(GemmArgs g) {
   const int wm = wid >> 1, wn = wid & 1;
 
   // XCD-aware bijective remap (as gemm_fast_kernel)
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7;
-  const int lid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int nN = (g.N + BN_ - 1) / BN_, nM = (g.M + BM - 1) / BM;
   const int z = lid / (nN * nM);
   const int rem = lid - z * nN * nM;
@@ -152,17 +135,7 @@ __global__ void __launch_bounds__(256, 1) gemm_nt_kernel(GemmArgs g) {
     }
 
   for (int kt = 0; kt < nkt; ++kt) {
-    const int ahead = min(P - 1, nkt - 1 - kt);  // tiles allowed to stay in flight
-    if constexpr (P >= 3) {
-      if (ahead >= 2) wait_vm<2 * LPT>();
-      else if (ahead == 1) wait_vm<LPT>();
-      else wait_vm<0>();
-    } else if constexpr (P == 2) {
-      if (ahead >= 1) wait_vm<LPT>();
-      else wait_vm<0>();
-    } else {
-      wait_vm<0>();
-    }
+    ring_wait<P, LPT>(min(P - 1, nkt - 1 - kt));  // tiles allowed to stay in flight
     raw_barrier();
     if (kt + P < nkt) {
       char* st = smem_raw + ((kt + P) % NST) * STAGE;

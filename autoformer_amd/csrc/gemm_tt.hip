@@ -7,7 +7,7 @@
 // projection (Norm.py:40-50).
 //
 // Both operands are stored frame-major, so a K-tile is 64 frame rows x 128 columns: it is
-// copied global -> LDS row by row with global_load_lds_dwordx4 (256-B rows, 16-B chunks
+// copied global -> LDS row by row with 16-B LDS-DMA fills (glds16; 256-B rows, 16-B chunks
 // XOR-swizzled as chunk ^ (((row&3)<<2) | ((row>>2)&3)) via the source address) and the
 // MFMA fragments, which need 8 consecutive frames per lane, are read with the gfx950
 // transposing LDS read ds_read_b64_tr_b16 (cdna_hip_programming.md §5.5 T10, layout (b):
@@ -22,24 +22,11 @@
 namespace avcg {
 namespace {
 
-__device__ __attribute__((aligned(16))) unsigned int g_zero16_tt[4] = {0u, 0u, 0u, 0u};
-
 constexpr int TROW = 256;          // LDS bytes per frame row of a 128-column tile
 constexpr int TSTAGE_OP = FBK * TROW;  // one operand's K-tile: 16 KiB
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* gbl_ptr_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4* lds_s4_ptr;
-
-__device__ __forceinline__ void glds16(const void* src, char* lds) {
-  __builtin_amdgcn_global_load_lds((gbl_ptr_t)src, (lds_ptr_t)lds, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void raw_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 __device__ __forceinline__ int tswz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
@@ -92,7 +79,7 @@ struct TtLoader {
         ok = ok && t2 >= 0 && t2 < t_in;
         frame = (long long)b * t_in + t2;
       }
-      const void* src = ok ? (const void*)(base + frame * ld + coff) : (const void*)g_zero16_tt;
+      const void* src = ok ? (const void*)(base + frame * ld + coff) : (const void*)g_zero16;
       glds16(src, lds_tile + 4 * (NW * i + w) * TROW);
     }
   }
@@ -145,9 +132,7 @@ __global__ void __launch_bounds__(256, 2) gemm_tt_kernel(GemmArgs g) {
   const int tid = threadIdx.x, wid = tid >> 6;
   const int wm = wid >> 1, wn = wid & 1;
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q = nwg >> 3, rr = nwg & 7, xcd = bid & 7;
-  const int lid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const int nN = (g.N + BN_ - 1) / BN_, nM = (g.M + BM - 1) / BM;
   const int z = lid / (nN * nM);
   const int rem = lid - z * nN * nM;
@@ -267,9 +252,7 @@ __global__ void __launch_bounds__(256, 2) gemm_tt_halo_kernel(GemmArgs g) {
   const int wm = wid >> 1, wn = wid & 1;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, rr = nwg & 7, xcd = bid & 7;
-  const int lid = (xcd < rr ? xcd * (q8 + 1) : rr * (q8 + 1) + (xcd - rr) * q8) + (bid >> 3);
+  const int lid = xcd_remap(blockIdx.x, gridDim.x);
   const OpDev& X = g.b;
   const int chans = X.chans, pad = X.pad, T = X.t_out;
   const int nC = chans / CW, nM = (g.M + BM - 1) / BM;
@@ -311,7 +294,7 @@ __global__ void __launch_bounds__(256, 2) gemm_tt_halo_kernel(GemmArgs g) {
     for (int i = 0; i < 2; ++i) {
       const int f = f0 - pad + hrow[i];
       const bool ok = hrow[i] < FBK + TAPS - 1 && f >= u0 && f < u0 + T;
-      const void* src = ok ? (const void*)(xb + (long long)f * ldx + c0 + hchk[i]) : (const void*)g_zero16_tt;
+      const void* src = ok ? (const void*)(xb + (long long)f * ldx + c0 + hchk[i]) : (const void*)g_zero16;
       glds16(src, st + (2 * wid + i) * 1024);
     }
   };
@@ -336,13 +319,7 @@ __global__ void __launch_bounds__(256, 2) gemm_tt_halo_kernel(GemmArgs g) {
   for (int p = 0; p < P; ++p)
     if (p < nkt) issue_tile(smem_raw + p * HSTAGE, tb + p);
   for (int kt = 0; kt < nkt; ++kt) {
-    const int ahead = min(P - 1, nkt - 1 - kt);  // K-tiles allowed to stay in flight
-    if constexpr (P >= 2) {
-      if (ahead >= 1) wait_vm<LPT>();
-      else wait_vm<0>();
-    } else {
-      wait_vm<0>();
-    }
+    ring_wait<P, LPT>(min(P - 1, nkt - 1 - kt));  // K-tiles allowed to stay in flight
     raw_barrier();
     if (kt + P < nkt) issue_tile(smem_raw + ((kt + P) % NST) * HSTAGE, tb + kt + P);
     const char* As = smem_raw + (kt % NST) * HSTAGE;

@@ -336,8 +336,8 @@ int avc_lstm2_bwd(const float* dh1, const float* c0, const float* gates0, const 
                   void* dg0_bf16, float* dg1, void* dg1_bf16, void* buf, float* db_part, void* stream);
 
 /* Which deep-ring kernel the last avc_gemm on this host thread launched (tests, tools): 0 none (an
- * older kernel), 1 gemm_ring_kernel, 2 the 128-row halo conv (conv_ring_kernel, its BN-backward
- * form included), 3 the one-utterance halo conv (conv_utt_kernel, 128 < T <= 192).  (The
+ * older kernel), 1 gemm_ring_kernel, 2 the 128-row halo conv (conv_ring.hip's conv_ring_kernel<128>,
+ * its BN-backward form included), 3 its one-utterance form (conv_ring_kernel<192>, 128 < T <= 192).  (The
  * warp-specialised halo conv and the 32-deep-slot ring, once 4 and 5, no longer exist: a forced
  * configuration the ring has no instance for is declined.)  Replaces no reference interface. */
 int avc_gemm_ring_last(void);
@@ -347,7 +347,7 @@ int avc_gemm_ring_last(void);
  * argument.  0 = nothing ran: the call was refused, M == 0 or N == 0, or the
  * kernel's launch failed.  Otherwise
  *   bits 0-3  family : 1 generic kernel (gemm.hip), 2 gemm_fast_kernel, 3 gemm_nt.hip,
- *                      4 gemm_conv.hip, 5 gemm_tt.hip, 6 the ring kernels (gemm_ring.hip)
+ *                      4 gemm_conv.hip, 5 gemm_tt.hip, 6 the ring kernels (gemm_ring.hip, conv_ring.hip)
  *   bits 4-7  variant: fast / nt: 1 = 64-column tiles, 2 = 128-column tiles;
  *                      tt: 1 plain, 2 window stream, 3 halo;
  *                      ring: avc_gemm_ring_last's value (1 gemm, 2 halo conv, 3 one-utterance conv);

@@ -4,7 +4,7 @@ variant avc_gemm_last_path can name is the expected value of some row).
 
 A row is (descriptor recipe, expected witness).  Shapes are the smallest that cross a tile edge in
 every dimension (row tiles of 128, column tiles of 64 or 128, K tiles of 32 / 64) and land on the
-listed kernel by the predicates of gemm_impl, gemm_ring_launch_, gemm_conv_launch, gemm_nt_launch,
+listed kernel by the predicates of gemm_impl, gemm_ring_launch, gemm_conv_launch, gemm_nt_launch,
 gemm_tt_launch and make_op (gemm*.hip); the reason is noted per group.
 """
 from dataclasses import dataclass, field
@@ -39,7 +39,7 @@ class Case:
     comp: str = "bf16"
     a: dict = field(default_factory=op)
     b: dict = field(default_factory=op)
-    ring: int = -1         # avc_gemm_set_ring mode: -1 default policy, 0 off
+    ring: int = -1         # avc_gemm_set_ring mode: -1 default policy, 0 off, 1 forced to the 128 x 128 x 4 tile
     batch: int = 1
     bsum: bool = False     # the batch summed into one C (c_batch_stride == 0)
     fold: bool = False     # contiguous A / C batches sharing B: gemm_impl folds them into one product
@@ -181,6 +181,9 @@ for bn in (None, 0):
 conv("conv-bn-fin", 3, 37, 32, 72, CONV, bn=1, bias=True)
 conv("conv-bnb", 3, 37, 32, 72, CONV | PATH_BNB, bnb=2)  # the ring takes avc_gemm_bnb on its halo tile only
 conv("ring-halo-bnb", 2, 128, 32, 128, RING_HALO | PATH_BNB, family="ring", bnb=2)  # ring_bnb_epilogue
+# the straddling BN-backward instance, which only a forced configuration reaches (T % 128 != 0): M = 150 is two
+# row tiles, the second partial, both spanning utterances; N % 8 == 0 and ldc == N as avc_gemm_bnb needs
+conv("ring-halo-bnb-straddle", 3, 50, 32, 72, RING_HALO | PATH_BNB, family="ring", ring=1, bnb=2)
 
 # ------------------------------------------------------------------ gemm_tt.hip (bf16, both K-strided)
 TT, TTW, TTH = gemm_path(PATH_TT, 1), gemm_path(PATH_TT, 2), gemm_path(PATH_TT, 3)

@@ -41,7 +41,8 @@ _SHARED = {}   # operand values and products shared by rows of one shape (comput
 def _ring(mode):
     from autoformer_amd import _lib
 
-    _lib.call("avc_gemm_set_ring", mode, 0, 0, 0, 8, 2)
+    bm, bn, nst = (128, 128, 4) if mode == 1 else (0, 0, 0)  # the forced tile of the rows with ring=1
+    _lib.call("avc_gemm_set_ring", mode, bm, bn, nst, 8, 2)
 
 
 @pytest.fixture(autouse=True)

@@ -1165,7 +1165,7 @@ def test_conv_bn_fused_finalize(B, T, Cin, Cout):
     """The halo conv kernels with the BN finalize in their epilogue (the forward conv + BN of every
     ConvNorm layer) against the same conv with the separate finalize: y, partials, mean / rstd /
     scale / shift and the running statistics.  The utterance-aligned shape with Cout >= 128
-    ((64, 128, 512, 512)) takes the eight-wave ring kernel (gemm_ring.hip conv_ring_kernel: ring / halo
+    ((64, 128, 512, 512)) takes the eight-wave ring kernel (conv_ring.hip conv_ring_kernel: ring / halo
     conv), the others gemm_conv.hip -- (8, 176, 512, 80) and (2, 300, 32, 64) too: Cout < 128 keeps
     them off the ring and off its one-utterance tile."""
     import autoformer_amd as A

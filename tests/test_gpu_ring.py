@@ -1,10 +1,11 @@
-"""The deep-ring GEMM kernels (gemm_ring.hip) against fp32 references of the same op:
+"""The deep-ring kernels (gemm_ring.hip, conv_ring.hip) against fp32 references of the same op:
 
   * gemm_ring_kernel at every tile configuration, with ragged M / N / K (zero-granule tails), bias,
     residual, accumulate, bf16 twin and the batch fold of shared-B products
     (reference: the nn.Linear / Conv1d(k=1) products of factory/MLPMixer.py:16-33,58-92);
   * conv_ring_kernel (5-tap 'same' Conv1d, factory/Norm.py:21-28) on utterance-aligned and
-    straddling tiles, with the BatchNorm statistics + finalize epilogue;
+    straddling 128-row tiles and on the one-utterance 192-row tile, with the BatchNorm statistics +
+    finalize epilogue;
   * the fused GELU epilogues (avc_gemm_desc.c_bf16_act / act_grad_of, MLPMixer.py:9-23) and the
     bias-gradient column sums (col_sum), on the ring kernel and on the fallback pass after the
     older kernels.
@@ -55,7 +56,7 @@ def _rel(a, b):
 
 CFGS = [(256, 256, 2), (256, 128, 3), (128, 128, 4), (128, 128, 3), (128, 256, 3), (256, 128, 2),
         (256, 256, 14), (256, 128, 15), (128, 128, 16), (128, 128, 2)]
-# nst 14 / 15 / 16 named the 32-deep-slot ring (nst 10 + n), which is gone: gemm_ring_launch_ has no such
+# nst 14 / 15 / 16 named the 32-deep-slot ring (nst 10 + n), which is gone: gemm_ring_launch has no such
 # configuration and declines it, so those three rows run the 64-wide gemm_nt.hip tile (the witness below)
 
 
@@ -127,7 +128,7 @@ def test_ring_default_policy_and_batch_fold():
                                                   (3, 176, 96, 200, True), (2, 50, 32, 64, True)])
 @pytest.mark.parametrize("bn", [False, True])
 def test_conv_ring(B, T, Cin, Cout, forced, bn):
-    """conv_ring_kernel (ring / halo conv: the default policy on utterance-aligned tiles, forced on
+    """conv_ring_kernel<128> (ring / halo conv, conv_ring.hip: the default policy on utterance-aligned tiles, forced on
     straddling ones) and, with the ring off, gemm_conv.hip on the same conv."""
     from autoformer_amd import kernels as K
 
@@ -166,7 +167,7 @@ def test_conv_ring(B, T, Cin, Cout, forced, bn):
 @pytest.mark.parametrize("B,T,Cin,Cout", [(4, 176, 64, 200), (64, 176, 512, 512), (3, 160, 96, 136), (2, 192, 32, 128)])
 @pytest.mark.parametrize("bn", [False, True])
 def test_conv_utterance_tile(B, T, Cin, Cout, bn):
-    """conv_utt_kernel: one utterance per 192-row tile (128 < T <= 192; T = 176 is C4 / C5), rows
+    """conv_ring_kernel<192>: one utterance per 192-row tile (128 < T <= 192; T = 176 is C4 / C5), rows
     T..191 computed from zero halo rows and not stored; the BatchNorm statistics as one T-row tile
     per workgroup, merged by the in-kernel finalize (bn_rows = T)."""
     from autoformer_amd import _lib

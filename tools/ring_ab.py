@@ -1,4 +1,4 @@
-"""A/B of the deep-ring NT GEMM (gemm_ring.hip) against the older kernels on the C2 / C4 product
+"""A/B of the deep-ring NT GEMM and halo conv (gemm_ring.hip, conv_ring.hip) against the older kernels on the C2 / C4 product
 shapes, interleaved in one process (cdna_hip_programming.md §5.4 rule 24), random operands, with
 an fp32 reference check of every configuration.
 
@@ -75,13 +75,8 @@ CONFIGS = [("old", (0, 0, 0, 0, 0, 1)), ("auto", (-1, 0, 0, 0, 8, 1)), ("halo", 
            ("128x128x4", (1, 128, 128, 4, 8, 1)), ("256x128x3", (1, 256, 128, 3, 8, 1)),
            ("256x256x2", (1, 256, 256, 2, 8, 1)), ("128x256x3", (1, 128, 256, 3, 8, 1)),
            ("auto-gm4", (-1, 0, 0, 0, 4, 1)), ("auto-gm16", (-1, 0, 0, 0, 16, 1)),
-           # timing ablations of the halo conv (wrong results): its loads alone / its reads + MFMAs alone
-           ("halo-loads", (-1, 0, 0, 0, 8, 3)), ("halo-math", (-1, 0, 0, 0, 8, 4)),
-           ("halo-contig", (-1, 0, 0, 0, 8, 5)),
-           # the warp-specialised halo conv (4 MMA waves of 64 x 64 + 4 loader waves)
-           ("halo-ws", (-1, 0, 0, 0, 8, 6)),
-           ("halo-mfma", (-1, 0, 0, 0, 8, 7)), ("halo-reads", (-1, 0, 0, 0, 8, 8)),
-           ("halo-prio", (-1, 0, 0, 0, 8, 9)), ("halo-noutt", (-1, 0, 0, 0, 8, 10))]
+           # win 10: the halo convs without the one-utterance tile (named with --configs only)
+           ("halo-noutt", (-1, 0, 0, 0, 8, 10))]
 
 
 def main():
