@@ -53,14 +53,18 @@ constexpr size_t persist2_lds() {
 
 // ---- LDS-DMA staging of the backward's hand-off payload: 16-B global_load_lds fills, sc1 like every
 // other load of handed-off bytes, retired by counted s_waitcnt vmcnt(n) + s_barrier.
-__device__ __attribute__((aligned(16))) unsigned g_zero16_l2[4] = {0u, 0u, 0u, 0u};  // source of zero rows
+__device__ __attribute__((aligned(16))) unsigned g_zero_l2[256] = {};  // source of zero rows: one 1-KiB fill
 typedef __attribute__((address_space(3))) void* l2_lds_ptr;
 typedef const __attribute__((address_space(1))) void* l2_gbl_ptr;
 // 16-B LDS fragment read as inline asm: the compiler's waitcnt pass would otherwise wait for every
-// LDS-DMA in flight (the next chunk's) before it
+// LDS-DMA in flight (the next chunk's) before it.  OFF is the instruction's immediate byte offset
+// (< 64 KiB), so the reads of a chunk tile share one address register: with an address VGPR per read
+// the backward spilled weight fragments to scratch.
+template <int OFF>
 __device__ __forceinline__ bf16x8 l2_ds_read16(unsigned addr) {
+  static_assert(OFF >= 0 && OFF < 65536, "ds_read offset field is 16 bits");
   u32x4_t v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
   return __builtin_bit_cast(bf16x8, v);
 }
 // the block's quit word, read the same way: before a plain LDS read the compiler waits for the previous
@@ -84,6 +88,13 @@ __device__ __forceinline__ void l2_lds_barrier() {
 template <int N>
 __device__ __forceinline__ void l2_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// The same wait for everything, as an instruction the compiler sees.  Its own bookkeeping of what is in
+// flight follows every static path (a load under one `if`, its use under another), and where it believes
+// a load pending it puts s_waitcnt vmcnt(0) in front of the next write of that register, on every tick.
+// Placed where nothing is in flight any more, this costs nothing and clears that bookkeeping.
+__device__ __forceinline__ void l2_drain_vm() {
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt and lgkmcnt left alone
 }
 // Waves 1..7: the staged outputs of tick kp (all 512 cells) to HBM.  (16-B value-major stores
 // of the same bytes measured slower per tick: 5.18 vs 4.99 us.)
@@ -112,7 +123,10 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_fwd(Persist2Args a) {
   // The measured schedule (each alternative was compiled and timed; the other values are gone):
   constexpr int SB = 2;       // scheduling fence every SB k-blocks of the product (without one the compiler
                               // hoists the A fragment reads and spills weight fragments)
-  constexpr int LB = 2;       // payload loads in LB batches (1 batch: slower)
+  constexpr int LB = 2;       // payload loads in LB batches.  1 batch (all eight loads in flight before one wait;
+                              // 253 VGPRs, no scratch, NLW = 4) is no faster: per tick, start -> payload in LDS
+                              // 2.48 -> 2.46 us, products 1.47 -> 1.51, -> published 0.82 -> 0.84, period 4.83 ->
+                              // 4.88; isolated 656.7 -> 655.6 us (profiles/lstm2_poll_ab.txt)
   constexpr bool OS = false;  // the previous tick's outputs are stored after the products (true: under the
                               // payload loads -- slower)
   constexpr int G = 4 * H, AP = H + 8, NR = H / QJU, NKQ = H / 128;  // k-blocks per K quarter
@@ -325,6 +339,8 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* red = reinterpret_cast<float*>(smem_raw);                     // [w][L][16][16] (in tile 0)
   bf16* ds16 = reinterpret_cast<bf16*>(red + 8 * 2 * QRG * QJU);       // [L][16][4 gates x 16] (in tile 0)
+  float* st32 = reinterpret_cast<float*>(smem_raw + CB);              // [4 gates][64 cells]: wave 0's dG (in
+                                                                       // tile 1, dead after the last chunk)
   bf16x8* wlb = reinterpret_cast<bf16x8*>(smem_raw + 2 * CB);          // [w][BNLW][64]
   int* quit = reinterpret_cast<int*>(wlb + 8 * BNLW * 64);
   static_assert((8 * 2 * QRG * QJU * 4 + 2 * QRG * 4 * QJU * 2) <= CB, "partials fit a chunk tile");
@@ -354,19 +370,22 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
       }
   }
   // this wave's 8 LDS-DMA fills per chunk: q = 8w + i -> layer q >> 5, row (q >> 1) & 15, half q & 1
-  // (1 KiB = 512 gate rows): wave-uniform bases + the lane's 16-B offset; rows past the batch read
-  // the zero granule
-  const long long slot_el = (long long)B * G;  // parity slot stride (elements)
+  // (1 KiB = 512 gate rows): a wave-uniform base, kept in SGPRs, + the lane's 16-B offset (one register
+  // pair for all fills instead of 64-bit vector bases held across the tick); rows past the batch read the
+  // zero KiB
+  const unsigned lane16 = lane * 16;
   auto issue = [&](int c, int slot) {
     char* tile = smem_raw + (c & 1) * CB;
+    // (opaque, or the compiler folds the loop-invariant lane offset into a 64-bit vector base of its own)
+    unsigned l16 = lane16;
+    asm volatile("" : "+v"(l16));
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int q = 8 * w + i, l = q >> 5, row = (q >> 1) & 15, half = q & 1;
-      const bf16* src = row < rows ? a.pay + ((long long)(l * 2 + slot) * B + b0 + row) * G + c * BKC + half * 512 +
-                                         lane * 8
-                                   : reinterpret_cast<const bf16*>(g_zero16_l2);
-      __builtin_amdgcn_global_load_lds((l2_gbl_ptr)src, (l2_lds_ptr)(tile + ((l * QRG + row) * BCP + half * 512) * 2),
-                                       16, 0, AUX_SC1);
+      const bf16* src = row < rows ? a.pay + ((long long)(l * 2 + slot) * B + b0 + row) * G + c * BKC + half * 512
+                                   : reinterpret_cast<const bf16*>(g_zero_l2);
+      __builtin_amdgcn_global_load_lds((l2_gbl_ptr)(reinterpret_cast<const char*>(src) + l16),
+                                       (l2_lds_ptr)(tile + ((l * QRG + row) * BCP + half * 512) * 2), 16, 0, AUX_SC1);
     }
   };
   if (tid == 0) *quit = 0;
@@ -376,6 +395,7 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
   float dc = 0.f;
   float sb0 = 0.f, sb1 = 0.f, sb2 = 0.f, sb3 = 0.f;  // this cell's dG summed over its steps (dbp)
   const unsigned quit_addr = l2_lds_addr(quit);
+  l2_drain_vm();  // the weight fragments: otherwise waited for at their first use, inside every tick's chunk 0
   __syncthreads();
 
   for (int k = 0; k <= T; ++k) {
@@ -383,60 +403,82 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
     const bool act = (L == 1 ? k < T : k >= 1) && cv;
     if (k < T) stamp(a.trace, T, k, 0);
     f32x4 p1 = {0.f, 0.f, 0.f, 0.f}, p0 = {0.f, 0.f, 0.f, 0.f};
-    // per-cell inputs of this step (independent of the exchange: issued first).  The layer's pointers
-    // come by select on the wave-uniform L: indexed by a per-thread L they were loaded from the argument
-    // block through vector memory, each with a wait for everything older, on every tick.
-    float dhu = 0.f, ct = 0.f, cp = 0.f, gi = 0.f, gf = 0.f, gg = 0.f, go = 0.f;
-    if (act) {
-      const float* callL = L ? a.call[1] : a.call[0];
-      const long long oh = ((long long)cb * T + t) * H + cj;
-      if (L == 1) dhu = a.dhout1[oh];
-      ct = callL[oh];
-      cp = t > 0 ? callL[oh - H] : 0.f;
-      const float* gp = (L ? a.gall[1] : a.gall[0]) + ((long long)cb * T + t) * G + cj;
-      gi = gp[0];
-      gf = gp[H];
-      gg = gp[2 * H];
-      go = gp[3 * H];
-    }
+    // per-cell inputs of this step, independent of the exchange.  The layer's pointers come by select
+    // on the wave-uniform L: indexed by a per-thread L they were loaded from the argument block through
+    // vector memory, each with a wait for everything older, on every tick.  c_{t-1} is loaded at every
+    // step (at t = 0 c_t's own address, the value dropped), so a wave with a live cell issues the same
+    // number of loads on every tick: wave 0 counts them (below).
+    // They are read under `act` alone and deliberately not zeroed here: a write to these registers at the
+    // head of the tick waits (vmcnt) for whatever the compiler believes in flight on them, in every wave.
+    float dhu, ct, cp, gi, gf, gg, go;
+    auto load_inputs = [&]() {
+      if (act) {
+        const float* callL = L ? a.call[1] : a.call[0];
+        const int bt = cb * T + t;  // (32-bit: the row index of a (B,T,.) array; one register less than cb * T in 64)
+        const long long oh = (long long)bt * H + cj;
+        if (L == 1) dhu = a.dhout1[oh];
+        ct = callL[oh];
+        cp = callL[t > 0 ? oh - H : oh];
+        const float* gp = (L ? a.gall[1] : a.gall[0]) + (long long)bt * G + cj;
+        gi = gp[0];
+        gf = gp[H];
+        gg = gp[2 * H];
+        go = gp[3 * H];
+      }
+    };
+    // Waves 1..7 issue them first, ahead of the exchange.  Wave 0 polls the flags, and the poll's wait
+    // for a flag word is a wait for every older access of the wave: it issues its inputs behind the
+    // first two chunks' fills instead (first used after the products), and its cells' dG are stored by
+    // wave 1 (below), so nothing of its own is in flight when it looks at the flags.
+    if (w != 0 || k == 0) load_inputs();
     if (k > 0) {
       if (w == 0 && !poll_flags(flags, NR, (unsigned)k, a.ctl, a.fault, a.spin)) *quit = 1;
       __syncthreads();
-      if (l2_ds_read_word(quit_addr)) return;  // block-uniform exit after a spin timeout
+      // block-uniform exit after a spin timeout, as a scalar branch with a drain: the compiler routes the exit
+      // through the loop's latch, a static path from the step's input loads to the loop's head that skips their
+      // use, and it then waits for them (vmcnt(0)) at the head of every tick
+      if (__builtin_amdgcn_readfirstlane(l2_ds_read_word(quit_addr))) {
+        l2_drain_vm();
+        return;
+      }
       if (k < T) stamp(a.trace, T, k, 1);
       const int slot = (k - 1) & 1;
       issue(0, slot);
       issue(1, slot);
+      // wave 0 (layer 0, rows 0..3 of the group: row 0 is always live, so the loads are issued): c_t,
+      // c_{t-1} and four gates = W0L loads behind its 16 fills
+      constexpr int W0L = 6;
+      if (w == 0) load_inputs();
 #pragma unroll
       for (int c = 0; c < BNC; ++c) {
         // this wave's fills of chunk c have landed (the next chunk's 8 may be in flight), then
         // every wave's
-        if (c < BNC - 1) l2_wait_vm<8>();
-        else l2_wait_vm<0>();
+        // (wave 0: its inputs lie between chunk 1's fills and chunk 2's)
+        if (c == BNC - 1) l2_drain_vm();
+        else if (w == 0 && c < 2) l2_wait_vm<8 + W0L>();
+        else l2_wait_vm<8>();
         asm volatile("s_barrier" ::: "memory");
         const unsigned base = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)(smem_raw + (c & 1) * CB) + aoff;
-        // XB k-blocks of A fragments at a time (the weight fragments hold ~180 VGPRs)
-        constexpr int XB = 1;
-#pragma unroll
-        for (int i2 = 0; i2 < KPW; i2 += XB) {
-          bf16x8 x0[XB], x1[XB];
-#pragma unroll
-          for (int i = 0; i < XB; ++i) {
-            x0[i] = l2_ds_read16(base + 64 * (i2 + i));
-            x1[i] = l2_ds_read16(base + QRG * BCP * 2 + 64 * (i2 + i));
-          }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int i = 0; i < XB; ++i) {
-            const int idx = c * KPW + i2 + i;
-            const bf16x8 wb = idx < NF0 ? f0[idx < NF0 ? idx : 0] : wl[(idx >= NF0 ? idx - NF0 : 0) * 64];
-            p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1[i], f1[c][i2 + i], p1, 0, 0, 0);
-            p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1[i], fi[c][i2 + i], p0, 0, 0, 0);
-            p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0[i], wb, p0, 0, 0, 0);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        // one k-block of A fragments at a time (the weight fragments hold ~180 VGPRs), read at immediate
+        // offsets from the tile's one base: layer 0's rows at 64 i, layer 1's at QRG * BCP * 2 + 64 i
+#define L2_KBLOCK(I)                                                                                       \
+  {                                                                                                        \
+    const bf16x8 x0 = l2_ds_read16<64 * (I)>(base), x1 = l2_ds_read16<QRG * BCP * 2 + 64 * (I)>(base);     \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                     \
+    __builtin_amdgcn_sched_barrier(0);                                                                     \
+    const int idx = c * KPW + (I);                                                                         \
+    const bf16x8 wb = idx < NF0 ? f0[idx < NF0 ? idx : 0] : wl[(idx >= NF0 ? idx - NF0 : 0) * 64];         \
+    p1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, f1[c][I], p1, 0, 0, 0);                               \
+    p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, fi[c][I], p0, 0, 0, 0);                               \
+    p0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, wb, p0, 0, 0, 0);                                     \
+    __builtin_amdgcn_sched_barrier(0);                                                                     \
+  }
+        static_assert(KPW == 4, "four k-blocks per wave and chunk");
+        L2_KBLOCK(0)
+        L2_KBLOCK(1)
+        L2_KBLOCK(2)
+        L2_KBLOCK(3)
+#undef L2_KBLOCK
         asm volatile("s_barrier" ::: "memory");  // every wave is done reading this tile
         if (c + 2 < BNC) issue(c + 2, slot);
       }
@@ -449,11 +491,16 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
     }
     l2_lds_barrier();
     if (k < T) stamp(a.trace, T, k, 2);
-    float dh = dhu;
+    l2_drain_vm();  // the step's inputs, used from here on (the fills were waited for above)
+    float dh = act && L == 1 ? dhu : 0.f;
 #pragma unroll
     for (int ww = 0; ww < 8; ++ww) dh += red[((ww * 2 + L) * QRG + cr) * QJU + cu];
     float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
     if (act) {
+      // (the compiler otherwise starts tanh(c_t) and the t = 0 select right behind the loads, with a wait
+      // for them in front of the exchange)
+      asm volatile("" : "+v"(ct), "+v"(cp));
+      if (t == 0) cp = 0.f;
       const float tc = ftanh(ct);
       const float dcs = dc + dh * go * (1.f - tc * tc);
       v0 = dcs * gg * gi * (1.f - gi);  // d(pre i)
@@ -471,6 +518,12 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
     dsr[QJU] = (bf16)v1;
     dsr[2 * QJU] = (bf16)v2;
     dsr[3 * QJU] = (bf16)v3;
+    if (w == 0) {  // its cells' fp32 dG, for wave 1 to store
+      st32[lane] = v0;
+      st32[64 + lane] = v1;
+      st32[2 * 64 + lane] = v2;
+      st32[3 * 64 + lane] = v3;
+    }
     l2_lds_barrier();
     // ---- publish dG1_{t1} and dG0_{t0} (needed by tick k + 1; none after tick T - 1): wave 0, four
     // 16-B chunks per lane (2 layers x 16 rows x 8 chunks), then the flag
@@ -488,25 +541,31 @@ __global__ void __launch_bounds__(PNT, 1) lstm2_persist_bwd(Persist2BwdArgs a) {
     }
     __syncthreads();  // every wave's stores behind wave 0's flag (the payload doubling as the
                       // output instead measured slower, profiles/r6_lstm2_bwd_payload_out.txt)
-    if (act) {  // (wave 0 issues these after its flag: they stay off the hand-off's vmcnt wait)
-      const long long og = ((long long)cb * T + t) * G + cj;
-      float* dgL = L ? a.dg[1] : a.dg[0];
-      bf16* dg16L = L ? a.dg16[1] : a.dg16[0];
-      if (dgL) {
-        float* d = dgL + og;
-        d[0] = v0;
-        d[H] = v1;
-        d[2 * H] = v2;
-        d[3 * H] = v3;
+    // Waves 1..7 store their cells' dG; wave 1 (rows 4..7 of layer 0) also wave 0's (rows 0..3, the same
+    // units and step), read back from st32 before the next tick's barrier lets a fill into that tile.
+    auto store_dg = [&](bool on, int row, float x0, float x1, float x2, float x3) {
+      if (on) {
+        const long long og = (long long)((b0 + row) * T + t) * G + cj;
+        float* dgL = L ? a.dg[1] : a.dg[0];
+        bf16* dg16L = L ? a.dg16[1] : a.dg16[0];
+        if (dgL) {
+          float* d = dgL + og;
+          d[0] = x0;
+          d[H] = x1;
+          d[2 * H] = x2;
+          d[3 * H] = x3;
+        }
+        if (dg16L) {
+          bf16* d16 = dg16L + og;
+          d16[0] = (bf16)x0;
+          d16[H] = (bf16)x1;
+          d16[2 * H] = (bf16)x2;
+          d16[3 * H] = (bf16)x3;
+        }
       }
-      if (dg16L) {
-        bf16* d16 = dg16L + og;
-        d16[0] = (bf16)v0;
-        d16[H] = (bf16)v1;
-        d16[2 * H] = (bf16)v2;
-        d16[3 * H] = (bf16)v3;
-      }
-    }
+    };
+    if (w != 0) store_dg(act, cr, v0, v1, v2, v3);
+    if (w == 1) store_dg(k >= 1 && cb - 4 < B, cr - 4, st32[lane], st32[64 + lane], st32[2 * 64 + lane], st32[3 * 64 + lane]);
     if (k < T) stamp(a.trace, T, k, 3);
   }
   if (a.dbp) {
