@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # AVC_LIB_PATH: another build of the same ABI (same-box A/B timing of two builds, tools/ only)
 LIB_PATH = os.environ.get("AVC_LIB_PATH") or os.path.join(HERE, "libautovc_hip.so")
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip"]
+SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip"]
 ABI_VERSION = 31
 
 F32, BF16 = 0, 1
@@ -232,6 +232,15 @@ _SIGS_AUDIO = {
                               c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_int, c_void_p]),
 }
 
+# The sample-rate converter of include/autovc_hip_resample.h: a fourth header and a fourth table, added the
+# same way (no ABI bump; the first three tables are as they were); lib() binds all four.
+RESAMPLE_MAX_WEIGHTS = 131072
+_SIGS_RESAMPLE = {
+    "avc_resample": (c_int, [c_void_p, c_ll, c_int_p, c_void_p, c_int, c_void_p, c_int, c_int_p, c_void_p, c_int, c_int,
+                             c_int, c_void_p, c_ll, c_void_p]),
+    "avc_resample_tile": (c_int, [c_int, c_int, c_int]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -245,7 +254,8 @@ def build(verbose: bool = False, force: bool = False) -> str:
         # every header a translation unit includes (csrc/*.h, the public ABI header)
         deps = srcs + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", h)
                                                               for h in ("autovc_hip.h", "autovc_hip_dv.h",
-                                                                        "autovc_hip_audio.h")]
+                                                                        "autovc_hip_audio.h",
+                                                                        "autovc_hip_resample.h")]
         newest = max(os.path.getmtime(p) for p in deps)
         if os.path.getmtime(LIB_PATH) >= newest:
             return LIB_PATH
@@ -281,7 +291,8 @@ def lib():
             raise RuntimeError(f"libautovc_hip.so not found at {LIB_PATH}; run autoformer_amd._lib.build() "
                                "(or __graft_entry__.build()). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_DV.items()) + list(_SIGS_AUDIO.items()):
+        for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_DV.items()) + list(_SIGS_AUDIO.items())
+                                  + list(_SIGS_RESAMPLE.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -327,3 +338,8 @@ def exported_symbols_dv():
 def exported_symbols_audio():
     """The entry points of include/autovc_hip_audio.h (waveform -> log-mel)."""
     return list(_SIGS_AUDIO.keys())
+
+
+def exported_symbols_resample():
+    """The entry points of include/autovc_hip_resample.h (band-limited sample-rate conversion)."""
+    return list(_SIGS_RESAMPLE.keys())
