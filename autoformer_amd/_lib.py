@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # AVC_LIB_PATH: another build of the same ABI (same-box A/B timing of two builds, tools/ only)
 LIB_PATH = os.environ.get("AVC_LIB_PATH") or os.path.join(HERE, "libautovc_hip.so")
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip"]
+SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip"]
 ABI_VERSION = 31
 
 F32, BF16 = 0, 1
@@ -241,6 +241,14 @@ _SIGS_RESAMPLE = {
     "avc_resample_tile": (c_int, [c_int, c_int, c_int]),
 }
 
+# Per-utterance BatchNorm of include/autovc_hip_eval.h: a fifth header and a fifth table, added the same
+# way (no ABI bump; the first four tables are as they were); lib() binds all five.
+BN_SEG_LDS_ROWS = 240
+_SIGS_EVAL = {
+    "avc_bn_seg_apply": (c_int, [c_void_p, c_int, c_ll, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -255,7 +263,8 @@ def build(verbose: bool = False, force: bool = False) -> str:
         deps = srcs + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", h)
                                                               for h in ("autovc_hip.h", "autovc_hip_dv.h",
                                                                         "autovc_hip_audio.h",
-                                                                        "autovc_hip_resample.h")]
+                                                                        "autovc_hip_resample.h",
+                                                                        "autovc_hip_eval.h")]
         newest = max(os.path.getmtime(p) for p in deps)
         if os.path.getmtime(LIB_PATH) >= newest:
             return LIB_PATH
@@ -292,7 +301,7 @@ def lib():
                                "(or __graft_entry__.build()). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_DV.items()) + list(_SIGS_AUDIO.items())
-                                  + list(_SIGS_RESAMPLE.items())):
+                                  + list(_SIGS_RESAMPLE.items()) + list(_SIGS_EVAL.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -343,3 +352,8 @@ def exported_symbols_audio():
 def exported_symbols_resample():
     """The entry points of include/autovc_hip_resample.h (band-limited sample-rate conversion)."""
     return list(_SIGS_RESAMPLE.keys())
+
+
+def exported_symbols_eval():
+    """The entry points of include/autovc_hip_eval.h (per-utterance BatchNorm)."""
+    return list(_SIGS_EVAL.keys())

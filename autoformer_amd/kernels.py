@@ -310,6 +310,40 @@ def bn_apply(y, scale, shift, act, residual=None, out=None, twin16=None, out_bf1
     return attach_twin(out, o16)
 
 
+def bn_seg_apply(y, B, T, gamma, beta, eps, act, residual=None, out=None, twin16=None, out_bf16=False, C=None,
+                 want_stats=False):
+    """Per-utterance BatchNorm (avc_bn_seg_apply): y fp32 (B*T, ld) is B segments of T rows; each
+    (segment, channel) is normalised with its own mean and biased variance, then
+    act(gamma*(y - mean)*rstd + beta) (+ residual).  C: the first C of y's ld columns (default all);
+    residual and out share y's shape.  Results as bn_apply: a bf16 tensor (out_bf16) or fp32 with a bf16
+    twin in bf16 compute mode.  want_stats: returns (result, mean (B, C), rstd (B, C))."""
+    _dev(y, gamma, beta, residual, out)
+    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_contiguous():
+        raise TypeError(f"bn_seg_apply: y must be a contiguous fp32 (B*T, ld) tensor, got {y.dtype} {tuple(y.shape)}")
+    M, ld = y.shape
+    C = ld if C is None else int(C)
+    if M != int(B) * int(T):
+        raise ValueError(f"bn_seg_apply: y has {M} rows, B*T = {int(B) * int(T)}")
+    for name, t in (("residual", residual), ("out", out)):
+        if t is not None and (t.shape != y.shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError(f"bn_seg_apply: {name} must be contiguous fp32 of y's shape {tuple(y.shape)}")
+    mean = rstd = None
+    if want_stats:
+        mean, rstd = torch.empty(B, C, device=y.device), torch.empty(B, C, device=y.device)
+    if out_bf16:
+        if out is not None:
+            raise ValueError("bn_seg_apply: out is the fp32 result; out_bf16 allocates its own")
+        o32, o16 = None, torch.empty(M, ld, device=y.device, dtype=torch.bfloat16)
+        res = o16
+    else:
+        o32 = torch.empty(M, ld, device=y.device) if out is None else out
+        o16 = _twin_buf(o32, twin16)
+        res = attach_twin(o32, o16)
+    L.call("avc_bn_seg_apply", y.data_ptr(), F32, ld, int(B), int(T), C, gamma.data_ptr(), beta.data_ptr(), float(eps),
+           int(act), _ptr(residual), _ptr(o32), _ptr(o16), _ptr(mean), _ptr(rstd), stream())
+    return (res, mean, rstd) if want_stats else res
+
+
 def bn_bwd(dA, a, y, mean, rstd, gamma, act, need_dbias=True, into=None, twin16=None, beta=None, dy_bf16=False):
     """into = (dgamma, dbeta, dbias) buffers to accumulate into (direct gradient sink).
     a = None: the activation derivative comes from the pre-activation (y-mean)*rstd*gamma + beta.

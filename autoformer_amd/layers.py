@@ -477,6 +477,38 @@ def conv_dgrad(dy, B, T_in, T_out, w, pad, Wd, n_dx=None):
 
 
 # =============================================================================== conv + BN
+_PER_UTT = {"on": False}
+
+
+class per_utterance_bn:
+    """Context manager: inside it a train-mode conv + BatchNorm layer (ConvBNCore.conv_bn_act) takes its
+    statistics per utterance -- over each T_out-row segment of the frame-major batch (K.bn_seg_apply)
+    -- instead of over all B*T rows, so row block b of a batched forward is the B = 1 train-mode
+    forward of utterance b (how the reference converts, util/evaluate.py).  Forward only: entering
+    with gradients enabled raises, and so does a train-mode layer reached with them enabled.  The running
+    statistics and num_batches_tracked are not touched (a conversion does not change the model), and no
+    BN-backward link state (BnbLink) is recorded.  Eval-mode BatchNorm is per-row independent already and
+    keeps its path; outside the context nothing changes."""
+
+    def __enter__(self):
+        if torch.is_grad_enabled():
+            raise RuntimeError("per_utterance_bn is forward-only: enter it under torch.no_grad()")
+        self.prev = _PER_UTT["on"]
+        _PER_UTT["on"] = True
+        return self
+
+    def __exit__(self, *exc):
+        _PER_UTT["on"] = self.prev
+        return False
+
+
+def _per_utt_guard(core):
+    """Called where a conv + BN layer enters its autograd function (inside one, gradients are always
+    disabled): a train-mode layer under per_utterance_bn refuses to be part of a graph."""
+    if _PER_UTT["on"] and core.bn.training and torch.is_grad_enabled():
+        raise RuntimeError("per_utterance_bn is forward-only: run the model under torch.no_grad()")
+
+
 class ConvBNCore:
     """ConvNorm (Norm.py:4-37) + BatchNorm1d + activation, frame-major.
 
@@ -516,6 +548,14 @@ class ConvBNCore:
         conv, bn = self.conv, self.bn
         Co = conv.weight.shape[0]
         bf = K.compute() == K.BF16
+        if bn.training and _PER_UTT["on"]:
+            # per-utterance statistics (per_utterance_bn): the conv output stays fp32 in bf16 compute too,
+            # so the statistics do not come from rounded values; no epilogue partials, no finalize
+            y = torch.empty(M, Co, device=dev, dtype=torch.float32)
+            K.gemm(M, Co, Kdim, xop, wop, y, bias=conv.bias, row_bias=row_bias)
+            a = K.bn_seg_apply(y, M // T_out, T_out, bn.weight, bn.bias, bn.eps, self.act, residual,
+                               out_bf16=out_bf16 and bf and residual is None)
+            return a, (y, None, None, T_out)
         y = torch.empty(M, Co, device=dev, dtype=torch.bfloat16 if bf else torch.float32)
         a = None
         if bn.training:
@@ -661,7 +701,7 @@ class BnbLink:
 
 def _links(ctx, x, core, a, saved, fuse_prev):
     """Forward bookkeeping of the fused BN-backward statistics (BnbLink), bf16 training only."""
-    on = _BNB_ON and K.compute() == K.BF16 and core.bn.training
+    on = _BNB_ON and K.compute() == K.BF16 and core.bn.training and not _PER_UTT["on"]
     # only where the consumer's data-gradient conv runs on the halo conv ring (utterance-aligned
     # 128-frame tiles, >= 128 channels): on gemm_conv's epilogue the fusion measured slower (round 2)
     Co = core.conv.weight.shape[0]
@@ -713,6 +753,7 @@ def conv_bn(core: ConvBNCore, x, B, T_in, residual=None, out_bf16=False, fuse_pr
     enc_conv0 used by this layer alone -- its BatchNorm backward statistics ride on this layer's
     data-gradient GEMM (BnbLink)."""
     c, bn = core.conv, core.bn
+    _per_utt_guard(core)
     return _ConvBNFn.apply(x, core, B, T_in, residual, out_bf16, fuse_prev, c.weight, c.bias, bn.weight, bn.bias)
 
 
@@ -846,6 +887,7 @@ _FOLD = os.environ.get("AVC_FOLD", "1") != "0"
 
 def enc_conv0(core, mel2d, emb, B, T, out_bf16=False):
     c, bn = core.conv, core.bn
+    _per_utt_guard(core)
     Kw = c.weight.shape[2]
     if _FOLD and Kw == 2 * core.pad + 1 and T > 2 * core.pad and c.weight.shape[1] > mel2d.shape[1]:
         return _EncConv0FoldFn.apply(mel2d, emb, core, B, T, out_bf16, c.weight, c.bias, bn.weight, bn.bias)
