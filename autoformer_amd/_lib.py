@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # AVC_LIB_PATH: another build of the same ABI (same-box A/B timing of two builds, tools/ only)
 LIB_PATH = os.environ.get("AVC_LIB_PATH") or os.path.join(HERE, "libautovc_hip.so")
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip"]
+SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip"]
 ABI_VERSION = 31
 
 F32, BF16 = 0, 1
@@ -249,6 +249,14 @@ _SIGS_EVAL = {
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# Per-segment moments and AdaIN of include/autovc_hip_seg.h: a sixth header and a sixth table, added the same
+# way (no ABI bump; the first five tables are as they were); lib() binds all six.
+SEG_MOMENTS_LDS_FLOATS = 16368
+_SIGS_SEG = {
+    "avc_seg_moments": (c_int, [c_void_p, c_int, c_ll, c_void_p, c_void_p]),
+    "avc_adain_seg": (c_int, [c_void_p, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -264,7 +272,7 @@ def build(verbose: bool = False, force: bool = False) -> str:
                                                               for h in ("autovc_hip.h", "autovc_hip_dv.h",
                                                                         "autovc_hip_audio.h",
                                                                         "autovc_hip_resample.h",
-                                                                        "autovc_hip_eval.h")]
+                                                                        "autovc_hip_eval.h", "autovc_hip_seg.h")]
         newest = max(os.path.getmtime(p) for p in deps)
         if os.path.getmtime(LIB_PATH) >= newest:
             return LIB_PATH
@@ -301,7 +309,7 @@ def lib():
                                "(or __graft_entry__.build()). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_DV.items()) + list(_SIGS_AUDIO.items())
-                                  + list(_SIGS_RESAMPLE.items()) + list(_SIGS_EVAL.items())):
+                                  + list(_SIGS_RESAMPLE.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_SEG.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -357,3 +365,8 @@ def exported_symbols_resample():
 def exported_symbols_eval():
     """The entry points of include/autovc_hip_eval.h (per-utterance BatchNorm)."""
     return list(_SIGS_EVAL.keys())
+
+
+def exported_symbols_seg():
+    """The entry points of include/autovc_hip_seg.h (per-segment moments and AdaIN)."""
+    return list(_SIGS_SEG.keys())

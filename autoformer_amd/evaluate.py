@@ -4,6 +4,7 @@ generate_result :177-218; and the all-pairs wav export of generate.ipynb cell 8)
 
   plan_grid(src_lens, pairs, len_crop)     the crop draws of a grid, in the reference's order (host only)
   convert_grid(model, sources, emb)        every (source, target) conversion, batched where that is exact
+  grid_family(model)                       which batched path batch_families=True gives a model, or None
   Evaluator(config)                        the reference's class: same fields, same method names
   python -m autoformer_amd.evaluate        cosine summaries of a model, optionally the grid as wavs
 
@@ -14,10 +15,23 @@ statistics per utterance segment (bn_seg.hip), which makes each row of the batch
 The encoder output depends on the source alone, so it runs once per distinct (source, crop offset)
 instead of once per pair; only the decoder and the postnet run per pair.
 
-Batched: AutoVC (train or eval mode).  Every other family -- MetaConv / MetaPool (GroupNorm / pooling
-mixers), the AdaIN `*2` variants (whole-tensor moments of the batch) and `*_Adjust` -- is converted
-pair by pair through convert.Converter.get_trans_mel, the one-utterance path, on the crops the plan
-drew: the same draws, the same results, no batching.
+Batched by default: AutoVC (train or eval mode).  Every other family is converted pair by pair through
+convert.Converter.get_trans_mel, the one-utterance path, on the crops the plan drew: the same draws, the
+same results, no batching.
+
+Batched on request (batch_families=True, `--batch_families`; grid_family names the path):
+  MetaConv / MetaPool         their GroupNorms and mixers are per utterance already, their BatchNorms
+                              (the L = 344 and L = 88 segments of the decoder included) take the
+                              per-segment statistics like AutoVC's; len_crop must be 176
+  AutoVC2 / MetaConv2 / MetaPool2 with isAdain
+                              the AdaIN moments and the AdaIN itself are whole-tensor ops -- at B = 1 the
+                              utterance; under per_utterance_bn() they are taken per utterance segment
+                              (seg_moments.hip), in train and in eval mode.  The reference takes the
+                              postnet's statistics from the SOURCE mel and runs the encoder twice on it
+                              (util/evaluate.py:80-81); here one encoder pass per distinct (source, crop
+                              offset) gives the codes and the features, gathered per pair.
+Left pair by pair whatever the flag: the `*_Adjust` models.  Their target-side Adjust pass depends on
+each pair's own target crop and runs a 3-layer recurrence per pair -- a separate piece of work.
 
 Random draws follow the reference: crop offsets from numpy's global state (source, then target, per
 pair and per model), enrolment utterances and MetaDV windows from Python's `random`.
@@ -97,9 +111,30 @@ def batched_family(model, isAdjust=False, isAdain=False):
     return type(model) is AutoVC and not isAdjust and not isAdain
 
 
+def grid_family(model, isAdjust=False, isAdain=False):
+    """The batched path convert_grid(..., batch_families=True) takes for this model, by exact type:
+    "autovc" (AutoVC), "meta" (MetaConv, MetaPool), "adain" (AutoVC2, MetaConv2, MetaPool2 called with
+    isAdain) -- or None: the `*_Adjust` models, isAdjust, an AdaIN model called without isAdain, anything
+    else.  None stays on the pair-by-pair path."""
+    from .factory.AutoVC import AutoVC
+    from .factory.AutoVC2 import AutoVC2
+    from .factory.MetaConv import MetaConv
+    from .factory.MetaConv2 import MetaConv2
+    from .factory.MetaPool import MetaPool
+    from .factory.MetaPool2 import MetaPool2
+
+    if isAdjust:
+        return None
+    if type(model) in (AutoVC2, MetaConv2, MetaPool2):
+        return "adain" if isAdain else None
+    if isAdain:
+        return None
+    return {AutoVC: "autovc", MetaConv: "meta", MetaPool: "meta"}.get(type(model))
+
+
 @torch.no_grad()
 def convert_grid(model, sources, emb, pairs=None, len_crop=176, max_batch=64, rng=np.random, targets=None,
-                 isAdjust=False, isAdain=False, plan=None, device=None):
+                 isAdjust=False, isAdain=False, plan=None, device=None, batch_families=False):
     """Converted mels of every pair: (mels, pads) -- mels[i] the (len_crop, 80) float32 host mel of
     pairs[i] = (source, target) (default: all N*N pairs, source-major), pads[i] the zero frames that
     padded its source (cut them with mels[i][:len_crop - pads[i]], the reference's isPlay branch).
@@ -112,8 +147,19 @@ def convert_grid(model, sources, emb, pairs=None, len_crop=176, max_batch=64, rn
     pairs in chunks of at most max_batch, all under layers.per_utterance_bn() -- a train-mode model
     gives each row its B = 1 train-mode result and its BatchNorm buffers are left as they were; an
     eval-mode model takes its usual path.  Any other family (MetaConv / MetaPool, the AdaIN `*2`
-    variants, `*_Adjust`) is NOT batched: each pair goes through Converter.get_trans_mel on the planned
-    crops, exactly the one-utterance path."""
+    variants, `*_Adjust`) is NOT batched by default: each pair goes through Converter.get_trans_mel on
+    the planned crops, exactly the one-utterance path.
+
+    batch_families=True: every family for which grid_family is not None runs batched the same way --
+    MetaConv / MetaPool (len_crop 176 only: MetaBlock.frames raises otherwise) and, with isAdain, the
+    AdaIN `*2` variants, whose encoder pass also returns the per-row AdaIN features (the reference takes
+    them from the source mel); the decode gathers them by plan.pair_enc.  The plan, the draws, the pads
+    and the return shapes are those of the pair-by-pair path.  The reference's loop -- and the
+    pair-by-pair path here -- moves a train-mode model's BatchNorm running statistics and
+    num_batches_tracked with every forward; the batched path leaves the model as it was.  The `*_Adjust`
+    models stay pair by pair."""
+    if not isinstance(batch_families, (bool, np.bool_)):
+        raise TypeError(f"batch_families must be a bool, got {type(batch_families).__name__}")
     if int(max_batch) < 1:
         raise ValueError(f"max_batch must be >= 1, got {max_batch}")
     emb = np.asarray(emb, dtype=np.float32)
@@ -127,7 +173,11 @@ def convert_grid(model, sources, emb, pairs=None, len_crop=176, max_batch=64, rn
     if device is None:
         device = next(model.parameters()).device
     device = torch.device(device)
-    if not batched_family(model, isAdjust, isAdain):
+    if batch_families:
+        family = grid_family(model, isAdjust, isAdain)
+    else:
+        family = "autovc" if batched_family(model, isAdjust, isAdain) else None
+    if family is None:
         conv = Converter(model, len_crop, device)
         mels = []
         for i, (s, t) in enumerate(plan.pairs):
@@ -146,13 +196,21 @@ def convert_grid(model, sources, emb, pairs=None, len_crop=176, max_batch=64, rn
     e_rows = e_all[torch.tensor([s for s, _ in plan.enc_rows], device=device)]
     pair_enc = torch.tensor(plan.pair_enc, device=device)
     pair_trg = torch.tensor([t for _, t in plan.pairs], device=device)
-    out = []
+    out, feats = [], None
     with Lyr.per_utterance_bn():
-        codes = torch.cat([model.encoder.codes_flat(x_rows[k:k + K_].contiguous(), e_rows[k:k + K_].contiguous())
-                           for k in range(0, x_rows.shape[0], K_)])
+        chunks = [(x_rows[k:k + K_].contiguous(), e_rows[k:k + K_].contiguous()) for k in range(0, x_rows.shape[0], K_)]
+        if family == "adain":
+            # one encoder pass per row: the codes and the three [mean (rows,), std (rows,)] feature pairs
+            parts = [model.encoder.codes_and_features(x, e) for x, e in chunks]
+            codes = torch.cat([c for c, _ in parts])
+            feats = [[torch.cat([f[j][i] for _, f in parts]) for i in range(2)] for j in range(3)]
+        else:
+            codes = torch.cat([model.encoder.codes_flat(x, e) for x, e in chunks])
         for k in range(0, len(plan.pairs), K_):
             rows = pair_enc[k:k + K_]
-            _, psnt, _ = decode(model, x_rows[rows], codes[rows].contiguous(), e_all[pair_trg[k:k + K_]].contiguous())
+            f_rows = None if feats is None else [[f[0][rows].contiguous(), f[1][rows].contiguous()] for f in feats]
+            _, psnt, _ = decode(model, x_rows[rows], codes[rows].contiguous(), e_all[pair_trg[k:k + K_]].contiguous(),
+                                f_rows)
             out.append(psnt.squeeze(1).float().cpu().numpy())
     if device.type == "cuda":
         from . import kernels as K
@@ -296,9 +354,11 @@ class Evaluator:
     def get_cos_trans(self, cos_res):
         return get_cos_trans(cos_res)
 
-    def generate_result(self, models: list, sound_id=2, isAdjust=False, isAdain=False, max_batch=64):
+    def generate_result(self, models: list, sound_id=2, isAdjust=False, isAdain=False, max_batch=64,
+                        batch_families=False):
         """One (N, N, N) array per model: cos[source][target][k], the conversion source -> target of
-        utterance `sound_id` scored by the judge against speaker k's d-vector."""
+        utterance `sound_id` scored by the judge against speaker k's d-vector.  batch_families: passed
+        on to convert_grid (the Meta and AdaIN families batched too; `*_Adjust` stays pair by pair)."""
         from .embed import cos_scores
 
         if self.embedder is None:
@@ -308,7 +368,8 @@ class Evaluator:
         lens = [m.shape[0] for m in mels]
         plans = plan_grid(lens, None, self.len_crop, np.random, tgt_lens=lens, copies=len(models))
         trans = [convert_grid(m, mels, self._emb(), len_crop=self.len_crop, max_batch=max_batch, targets=mels,
-                              isAdjust=isAdjust, isAdain=isAdain, plan=p, device=self.device)[0]
+                              isAdjust=isAdjust, isAdain=isAdain, plan=p, device=self.device,
+                              batch_families=batch_families)[0]
                  for m, p in zip(models, plans)]
         # the judge's draws in the reference's order: pair after pair, model after model
         flat = [trans[k][i] for i in range(N * N) for k in range(len(models))]
@@ -387,6 +448,9 @@ def _parser():
     p.add_argument("--max_uttr_idx", type=int, default=60)
     p.add_argument("--sound_id", type=int, default=2)
     p.add_argument("--max_batch", type=int, default=64)
+    p.add_argument("--batch_families", action="store_true",
+                   help="batch the MetaConv / MetaPool and AdaIN (*2) grids too, not AutoVC's alone (*_Adjust "
+                        "stays pair by pair)")
     p.add_argument("--seed", type=int, help="seed numpy's and Python's random (the crop / enrolment draws)")
     return p
 
@@ -447,7 +511,8 @@ def main(argv=None):
     E = Evaluator(cfg)
     adjust, adain = args.model.endswith("_Adjust"), args.model.endswith("2")
     if args.embedder:
-        cos = E.generate_result([model], args.sound_id, adjust, adain, max_batch=args.max_batch)[0]
+        cos = E.generate_result([model], args.sound_id, adjust, adain, max_batch=args.max_batch,
+                                batch_families=args.batch_families)[0]
         rc, rc_other = E.get_cos_rc(cos)
         tr, tr_other = E.get_cos_trans(cos)
         print(f"reconstruction: cos to own speaker {rc:.4f}, to the others {rc_other:.4f}")
@@ -456,7 +521,8 @@ def main(argv=None):
         N = len(E.metadata)
         mels = [E._load(s, args.sound_id) for s in range(N)]
         trans, pads = convert_grid(model, mels, E._emb(), len_crop=args.len_crop, max_batch=args.max_batch,
-                                   targets=mels, isAdjust=adjust, isAdain=adain, device=args.device)
+                                   targets=mels, isAdjust=adjust, isAdain=adain, device=args.device,
+                                   batch_families=args.batch_families)
         written = export_grid_wavs(E.vocoder, trans, pads, all_pairs(N), [d[0] for d in E.metadata], args.wav_dir,
                                    args.len_crop)
         print(f"{args.wav_dir}: {len(written)} wavs")

@@ -42,12 +42,19 @@ def adain_encoder(Base):
             self._pre = [Lyr.ConvBNCore(s[0].conv, s[1], K.ACT_NONE) for s in self.feature_pre_extract]
 
         def pre_extract(self, mel, B, T):
-            """Frame-major mel -> (features-extracted frames, [[mean, std]] x 3)."""
+            """Frame-major mel -> (features-extracted frames, [[mean, std]] x 3).  Under
+            layers.per_utterance_bn() (train or eval mode: AdaIN has no running statistics) the moments
+            are those of each utterance's own T rows: three [mean (B,), std (B,)] pairs."""
             h, feats = mel, []
+            per_utt = Lyr._PER_UTT["on"]
             for core in self._pre:
                 h = Lyr.conv_bn(core, h, B, T)
-                m = V.moments(h)
-                feats.append([m[0], m[1]])
+                if per_utt:
+                    m = V.seg_moments(h, B)
+                    feats.append([m[:, 0].contiguous(), m[:, 1].contiguous()])
+                else:
+                    m = V.moments(h)
+                    feats.append([m[0], m[1]])
             return h, feats
 
         def codes_and_features(self, x, c_org):
@@ -76,11 +83,14 @@ class PostnetAdaIN(Postnet):
         self._comb = [Lyr.PackCache() for _ in range(3)]
 
     def frames(self, mel, B, T, features, residual=None):
+        """Under layers.per_utterance_bn() each utterance's T rows are normalised with their own moments
+        and take their own statistics: features are three [mean (B,), std (B,)] pairs."""
         h = mel
+        per_utt = Lyr._PER_UTT["on"]
         for core in self._convs:
             h = Lyr.conv_bn(core, h, B, T)
         for comb, cache, f in zip(self.feature_last_combine, self._comb, features):
-            h = V.adain(h, f[0], f[1])
+            h = V.adain_seg(h, B, f[0], f[1]) if per_utt else V.adain(h, f[0], f[1])
             h = MF.conv(h, comb[0].conv, cache, B, T)
         return h if residual is None else MF.add(residual, h)
 

@@ -1118,6 +1118,48 @@ def adain_bwd(g, x, mom, sigma):
     return dx, dmu, dsig
 
 
+def _seg_x(who, x, B):
+    """The argument checks of the per-segment ops: x a contiguous fp32 device tensor of B equal segments;
+    returns the segment length n."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError(f"{who}: x must be a contiguous fp32 tensor, got "
+                        f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    _dev(x)
+    B = int(B)
+    if B < 1 or x.numel() < B or x.numel() % B:
+        raise ValueError(f"{who}: x has {x.numel()} elements, not B = {B} segments of equal length (B*n == numel)")
+    return x.numel() // B
+
+
+def seg_moments(x, B, out=None):
+    """(B, 2) [mean, unbiased std] of each of the B contiguous segments of x (avc_seg_moments): torch.mean /
+    torch.std of that segment alone.  A frame-major (B*T, C) tensor gives the moments per utterance."""
+    n = _seg_x("seg_moments", x, B)
+    if out is None:
+        out = torch.empty(int(B), 2, device=x.device)
+    else:
+        _dev(out)
+        if out.shape != (int(B), 2) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise TypeError(f"seg_moments: out must be a contiguous fp32 ({int(B)}, 2) tensor")
+    L.call("avc_seg_moments", x.data_ptr(), int(B), n, out.data_ptr(), stream())
+    return out
+
+
+def adain_seg(x, B, mu, sigma):
+    """y_b = (x_b - mean(x_b)) / std(x_b) * sigma[b] + mu[b] per contiguous segment b of x, the moments of
+    each segment taken inside the same launch (avc_adain_seg); mu, sigma: (B,) fp32."""
+    n = _seg_x("adain_seg", x, B)
+    for name, t in (("mu", mu), ("sigma", sigma)):
+        if (not isinstance(t, torch.Tensor) or t.shape != (int(B),) or t.dtype != torch.float32
+                or not t.is_contiguous()):
+            raise ValueError(f"adain_seg: {name} must be a contiguous fp32 ({int(B)},) tensor, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    _dev(mu, sigma)
+    y = torch.empty_like(x)
+    L.call("avc_adain_seg", x.data_ptr(), int(B), n, mu.data_ptr(), sigma.data_ptr(), y.data_ptr(), stream())
+    return y
+
+
 def segsum(x, B, T, C, ld, out=None, accumulate=False):
     """out (B, C) = per-utterance sum over T of a C-column block of frame-major rows ld apart."""
     _dev(x)

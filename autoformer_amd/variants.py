@@ -3,6 +3,8 @@
 
   moments(x)           -> (2,) [x.mean(), x.std()]    factory/AutoVC2.py:58-60 (features)
   adain(x, mu, sigma)                                  factory/Norm.py:84-91
+  seg_moments(h, B)    -> (B, 2), adain_seg(h, B, mu, sigma): the two above per utterance segment of a
+                       batch (seg_moments.hip, forward only) -- what layers.per_utterance_bn() switches to
   step_select(h, ...)  nn.LSTM output [:, t, :]        factory/Adjust.py:39
   rownorm(e)           e / ||e||_2 per row             factory/Adjust.py:40-42
 
@@ -61,6 +63,25 @@ def _scalar(v, like):
 def adain(content, mu, std):
     """AdaIN.forward (Norm.py:84-91): (c - c.mean()) / c.std() * std + mu."""
     return _AdaINFn.apply(content, _scalar(mu, content), _scalar(std, content))
+
+
+def _forward_only(what):
+    if torch.is_grad_enabled():
+        raise RuntimeError(f"{what} is forward-only: call it under torch.no_grad()")
+
+
+def seg_moments(h, B):
+    """(B, 2) tensor [mean, std] of each of the B utterance segments of a frame-major (B*T, C) h: what
+    moments() gives at B = 1, per row block of a batch (seg_moments.hip).  Forward only."""
+    _forward_only("seg_moments")
+    return K.seg_moments(h.contiguous(), B)
+
+
+def adain_seg(h, B, mu, std):
+    """adain() per utterance segment: (h_b - h_b.mean()) / h_b.std() * std[b] + mu[b] with (B,) tensors
+    mu and std (seg_moments.hip).  Forward only."""
+    _forward_only("adain_seg")
+    return K.adain_seg(h.contiguous(), B, mu, std)
 
 
 class _StepSelectFn(torch.autograd.Function):
