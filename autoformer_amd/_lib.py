@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # AVC_LIB_PATH: another build of the same ABI (same-box A/B timing of two builds, tools/ only)
 LIB_PATH = os.environ.get("AVC_LIB_PATH") or os.path.join(HERE, "libautovc_hip.so")
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip"]
+SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip", "ragged.hip"]
 ABI_VERSION = 31
 
 F32, BF16 = 0, 1
@@ -257,6 +257,16 @@ _SIGS_SEG = {
     "avc_adain_seg": (c_int, [c_void_p, c_int, c_ll, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# The ragged-batch kernels of include/autovc_hip_ragged.h: a seventh header and a seventh table, added the
+# same way (no ABI bump; the first six tables are as they were); lib() binds all seven.
+_SIGS_RAGGED = {
+    "avc_bn_seg_ragged": (c_int, [c_void_p, c_int, c_ll, c_int, c_int, c_int, c_int_p, c_void_p, c_void_p, c_void_p,
+                                  c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "avc_row_mask": (c_int, [c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_int_p, c_void_p, c_void_p]),
+    "avc_bilstm_ragged_fwd": (c_int, [c_void_p, c_void_p, c_int_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                      c_int, c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -272,7 +282,8 @@ def build(verbose: bool = False, force: bool = False) -> str:
                                                               for h in ("autovc_hip.h", "autovc_hip_dv.h",
                                                                         "autovc_hip_audio.h",
                                                                         "autovc_hip_resample.h",
-                                                                        "autovc_hip_eval.h", "autovc_hip_seg.h")]
+                                                                        "autovc_hip_eval.h", "autovc_hip_seg.h",
+                                                                        "autovc_hip_ragged.h")]
         newest = max(os.path.getmtime(p) for p in deps)
         if os.path.getmtime(LIB_PATH) >= newest:
             return LIB_PATH
@@ -309,7 +320,8 @@ def lib():
                                "(or __graft_entry__.build()). There is no CPU fallback.")
         L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_DV.items()) + list(_SIGS_AUDIO.items())
-                                  + list(_SIGS_RESAMPLE.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_SEG.items())):
+                                  + list(_SIGS_RESAMPLE.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_SEG.items())
+                                  + list(_SIGS_RAGGED.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -370,3 +382,8 @@ def exported_symbols_eval():
 def exported_symbols_seg():
     """The entry points of include/autovc_hip_seg.h (per-segment moments and AdaIN)."""
     return list(_SIGS_SEG.keys())
+
+
+def exported_symbols_ragged():
+    """The entry points of include/autovc_hip_ragged.h (ragged batches of whole utterances)."""
+    return list(_SIGS_RAGGED.keys())

@@ -47,6 +47,30 @@ __device__ __forceinline__ float act_sig(float x) { return FAST ? fsig(x) : sigm
 template <bool FAST>
 __device__ __forceinline__ float act_tanh(float x) { return FAST ? ftanh(x) : tanhf(x); }
 
+// ---------------------------------------------------------------- small-H step (lstm_small.hip, ragged.hip)
+// broadcast lane N of each lane quad (DPP quad_perm, no LDS traffic)
+template <int N>
+__device__ __forceinline__ float quad_bcast(float v) {
+  constexpr int ctl = N | (N << 2) | (N << 4) | (N << 6);
+  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), ctl, 0xf, 0xf, false));
+}
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// sum_k w[k] * h[k] with the HM/4 float4 slices of h already in registers, as packed fp32 FMAs
+// (v_pk_fma_f32): four independent accumulation chains, so no FMA waits on its predecessor's result
+template <int HM>
+__device__ __forceinline__ float dot_regs(const f32x4 (&hv)[HM / 4], const f32x2 (&w)[HM / 2]) {
+  f32x2 a[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+#pragma unroll
+  for (int k = 0; k < HM / 4; ++k) {
+    a[(2 * k) & 3] = __builtin_elementwise_fma(f32x2{hv[k][0], hv[k][1]}, w[2 * k], a[(2 * k) & 3]);
+    a[(2 * k + 1) & 3] = __builtin_elementwise_fma(f32x2{hv[k][2], hv[k][3]}, w[2 * k + 1], a[(2 * k + 1) & 3]);
+  }
+  const f32x2 t = (a[0] + a[1]) + (a[2] + a[3]);
+  return t[0] + t[1];
+}
+
 // ---------------------------------------------------------------- buffer resources
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));

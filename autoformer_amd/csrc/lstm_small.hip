@@ -12,12 +12,7 @@ namespace {
 using namespace avcl;
 
 // =============================================================== packed FMA
-// broadcast lane N of each lane quad (DPP quad_perm, no LDS traffic)
-template <int N>
-__device__ __forceinline__ float quad_bcast(float v) {
-  constexpr int ctl = N | (N << 2) | (N << 4) | (N << 6);
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), ctl, 0xf, 0xf, false));
-}
+// (quad_bcast, f32x2 and dot_regs are in lstm_internal.h: ragged.hip's forward-only BiLSTM shares them)
 // sum over the lane quad (xor 1, then xor 2, as quad_perm)
 __device__ __forceinline__ float quad_sum(float v) {
   v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));
@@ -41,7 +36,6 @@ constexpr int SNT = 320;  // 4 compute waves + 1 flush wave
 constexpr int SD = 4;     // input lead, steps
 constexpr int SC = 16;    // output chunk, steps
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int OOB = 0x7FFFFFF0;  // buffer offset past every buffer here: the store is dropped
 
 // sum_k w[k] * v[k] over HM/4 float4 LDS slices of v; every slice is read before the first FMA
@@ -52,20 +46,6 @@ __device__ __forceinline__ float dot_lds(const float* __restrict__ v, const f32x
 #pragma unroll
   for (int k = 0; k < HM / 4; ++k) hv[k] = v4[k];
   // four independent accumulation chains, so no packed FMA waits on its predecessor's result
-  f32x2 a[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-#pragma unroll
-  for (int k = 0; k < HM / 4; ++k) {
-    a[(2 * k) & 3] = __builtin_elementwise_fma(f32x2{hv[k][0], hv[k][1]}, w[2 * k], a[(2 * k) & 3]);
-    a[(2 * k + 1) & 3] = __builtin_elementwise_fma(f32x2{hv[k][2], hv[k][3]}, w[2 * k + 1], a[(2 * k + 1) & 3]);
-  }
-  const f32x2 t = (a[0] + a[1]) + (a[2] + a[3]);
-  return t[0] + t[1];
-}
-
-// dot_lds with the h slices already in registers (the forward issues its deferred LDS writes between the
-// reads and the FMAs)
-template <int HM>
-__device__ __forceinline__ float dot_regs(const f32x4 (&hv)[HM / 4], const f32x2 (&w)[HM / 2]) {
   f32x2 a[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
 #pragma unroll
   for (int k = 0; k < HM / 4; ++k) {

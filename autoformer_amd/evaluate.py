@@ -398,10 +398,11 @@ def write_wav(path, audio, sample_rate=SAMPLE_RATE):
 def export_grid_wavs(vocoder, mels, pads, pairs, speakers, wav_dir, len_crop, max_batch=16):
     """generate.ipynb cell 8: <wav_dir>/<source speaker>/<source_id>_<target_id>.wav for every pair,
     the padded tail of the mel cut before vocoding (the isPlay=True call).  The vocoder runs batched
-    over mels of equal length (MelVocoder.inverse_frames)."""
+    over mels of equal length (MelVocoder.inverse_frames).  len_crop None: every mel at its own full length
+    (the --whole export; pads is ignored)."""
     by_len = {}
     for i, pad in enumerate(pads):
-        by_len.setdefault(len_crop - pad, []).append(i)
+        by_len.setdefault(mels[i].shape[0] if len_crop is None else len_crop - pad, []).append(i)
     written = []
     for T, idx in sorted(by_len.items()):
         for k in range(0, len(idx), max_batch):
@@ -451,6 +452,9 @@ def _parser():
     p.add_argument("--batch_families", action="store_true",
                    help="batch the MetaConv / MetaPool and AdaIN (*2) grids too, not AutoVC's alone (*_Adjust "
                         "stays pair by pair)")
+    p.add_argument("--whole", action="store_true",
+                   help="with --wav_dir: export every pair at the source's full length (convert.convert_whole, "
+                        "AutoVC only) instead of one len_crop window")
     p.add_argument("--seed", type=int, help="seed numpy's and Python's random (the crop / enrolment draws)")
     return p
 
@@ -479,6 +483,8 @@ def main(argv=None):
         raise SystemExit("--embedder_ckpt FILE is required with --embedder unless --det_init is given")
     if args.wav_dir and not args.vocoder_ckpt:
         raise SystemExit("--wav_dir needs --vocoder_ckpt FILE (a MelGAN generator state_dict)")
+    if args.whole and not args.wav_dir:
+        raise SystemExit("--whole exports wavs: it needs --wav_dir")
     if not args.embedder and not args.wav_dir:
         raise SystemExit("nothing to do: give --embedder (scores) and / or --wav_dir (wavs)")
     import autoformer_amd as A
@@ -520,6 +526,16 @@ def main(argv=None):
     if args.wav_dir:
         N = len(E.metadata)
         mels = [E._load(s, args.sound_id) for s in range(N)]
+        if args.whole:
+            from .convert import convert_whole
+
+            pairs, emb = all_pairs(N), E._emb()
+            trans = convert_whole(model, [mels[s] for s, _ in pairs], emb[[s for s, _ in pairs]],
+                                  emb[[t for _, t in pairs]], max_batch=args.max_batch, device=args.device)
+            written = export_grid_wavs(E.vocoder, trans, [0] * len(pairs), pairs, [d[0] for d in E.metadata],
+                                       args.wav_dir, None)
+            print(f"{args.wav_dir}: {len(written)} wavs")
+            return 0
         trans, pads = convert_grid(model, mels, E._emb(), len_crop=args.len_crop, max_batch=args.max_batch,
                                    targets=mels, isAdjust=adjust, isAdain=adain, device=args.device,
                                    batch_families=args.batch_families)

@@ -1336,3 +1336,106 @@ def metadv_head(e1, Y, S, w_dv, b_dv, w_out, b_out):
     L.call("avc_metadv_head", e1.data_ptr(), Y.data_ptr(), S, O, w_dv.data_ptr(), _ptr(b_dv), w_out.data_ptr(),
            _ptr(b_out), B, E, D, C, pred.data_ptr(), dvec.data_ptr(), stream())
     return pred, dvec
+
+
+# ------------------------------------------------------------------------- ragged batches (autovc_hip_ragged.h)
+class Lens:
+    """Frame counts of the B utterances of a ragged batch laid out (B*T, C): the host integers (checked by
+    the library before each launch) and the same values as an int32 device tensor (read by the kernels).
+    Rows lens[b] .. T - 1 of utterance b's block are padding."""
+
+    def __init__(self, lens, T, device):
+        vals = [int(v) for v in lens]
+        if not vals or min(vals) < 2 or max(vals) > int(T):
+            raise ValueError(f"Lens: every length must lie in 2..T = {int(T)}, got {vals}")
+        self.B, self.T, self.vals = len(vals), int(T), tuple(vals)
+        self.host = (L.c_int * self.B)(*vals)
+        self.dev = torch.tensor(vals, dtype=torch.int32, device=device)
+
+    def check(self, who, B, T, t):
+        if self.B != int(B) or self.T != int(T):
+            raise ValueError(f"{who}: lens describe B = {self.B}, T = {self.T}, the call has B = {int(B)}, T = {int(T)}")
+        if t.device != self.dev.device:
+            raise ValueError(f"{who}: the tensor is on {t.device}, its lengths on {self.dev.device}")
+
+
+def bn_seg_ragged(y, lens: Lens, gamma, beta, eps, act, residual=None, out=None, twin16=None, out_bf16=False, C=None,
+                  want_stats=False):
+    """bn_seg_apply with a length per segment (avc_bn_seg_ragged): segment b's statistics come from its own
+    rows 0 .. lens[b] - 1, its rows from lens[b] on are written as exact zeros (fp32 and bf16).  Arguments
+    and results as bn_seg_apply; B and T are those of `lens`."""
+    _dev(y, gamma, beta, residual, out)
+    B, T = lens.B, lens.T
+    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_contiguous():
+        raise TypeError(f"bn_seg_ragged: y must be a contiguous fp32 (B*T, ld) tensor, got {y.dtype} {tuple(y.shape)}")
+    M, ld = y.shape
+    C = ld if C is None else int(C)
+    if M != B * T:
+        raise ValueError(f"bn_seg_ragged: y has {M} rows, B*T = {B * T}")
+    lens.check("bn_seg_ragged", B, T, y)
+    for name, t in (("residual", residual), ("out", out)):
+        if t is not None and (t.shape != y.shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError(f"bn_seg_ragged: {name} must be contiguous fp32 of y's shape {tuple(y.shape)}")
+    mean = rstd = None
+    if want_stats:
+        mean, rstd = torch.empty(B, C, device=y.device), torch.empty(B, C, device=y.device)
+    if out_bf16:
+        if out is not None:
+            raise ValueError("bn_seg_ragged: out is the fp32 result; out_bf16 allocates its own")
+        o32, o16 = None, torch.empty(M, ld, device=y.device, dtype=torch.bfloat16)
+        res = o16
+    else:
+        o32 = torch.empty(M, ld, device=y.device) if out is None else out
+        o16 = _twin_buf(o32, twin16)
+        res = attach_twin(o32, o16)
+    L.call("avc_bn_seg_ragged", y.data_ptr(), F32, ld, B, T, C, lens.host, lens.dev.data_ptr(), gamma.data_ptr(),
+           beta.data_ptr(), float(eps), int(act), _ptr(residual), _ptr(o32), _ptr(o16), _ptr(mean), _ptr(rstd), stream())
+    return (res, mean, rstd) if want_stats else res
+
+
+def row_mask(x, lens: Lens, C=None):
+    """In place (avc_row_mask): rows t >= lens[b] of every utterance block of x (B*T, ld) become 0.0 over
+    the first C columns (default all) -- in x itself (fp32 or bf16) and, for an fp32 x that carries one,
+    in its bf16 twin too, so the two copies never disagree.  Returns x."""
+    _dev(x)
+    if x.dim() != 2 or not x.is_contiguous() or x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"row_mask: x must be a contiguous fp32 or bf16 (B*T, ld) tensor, got {x.dtype} {tuple(x.shape)}")
+    M, ld = x.shape
+    if M != lens.B * lens.T:
+        raise ValueError(f"row_mask: x has {M} rows, B*T = {lens.B * lens.T}")
+    lens.check("row_mask", lens.B, lens.T, x)
+    C = ld if C is None else int(C)
+    if x.dtype == torch.bfloat16:
+        x32, x16 = None, x
+    else:
+        x32, x16 = x, getattr(x, "_bf16", None)
+        if x16 is not None and (x16.shape != x.shape or x16.dtype != torch.bfloat16 or not x16.is_contiguous()):
+            raise TypeError("row_mask: the bf16 twin of x must be contiguous bf16 of x's shape")
+    L.call("avc_row_mask", _ptr(x32), _ptr(x16), ld, lens.B, lens.T, C, lens.host, lens.dev.data_ptr(), stream())
+    return x
+
+
+def bilstm_ragged_fwd(xproj, w_hh, lens: Lens, H, want_h32=True, want_h16=None):
+    """One bidirectional LSTM layer over a ragged batch, forward only (avc_bilstm_ragged_fwd): xproj fp32
+    (B*T, 2*4H) and W_hh fp32 (2*4H, H) as lstm_fwd takes them with dirs = 2; the backward direction of
+    utterance b starts at frame lens[b] - 1, and h is 0.0 in its rows from lens[b] on.  Returns h fp32
+    (B*T, 2H) with its bf16 twin attached (want_h16, default: bf16 compute mode), or the bf16 tensor alone
+    when want_h32 is off.  No cell states, no gates."""
+    _dev(xproj, w_hh)
+    B, T, H = lens.B, lens.T, int(H)
+    if H < 1 or H > 64:
+        raise ValueError(f"bilstm_ragged_fwd: H = {H} outside 1..64 (the encoder's small-H recurrence)")
+    if xproj.dtype != torch.float32 or tuple(xproj.shape) != (B * T, 8 * H) or not xproj.is_contiguous():
+        raise ValueError(f"bilstm_ragged_fwd: xproj must be a contiguous fp32 (B*T, 8H) = ({B * T}, {8 * H}) tensor")
+    if w_hh.dtype != torch.float32 or tuple(w_hh.shape) != (8 * H, H) or not w_hh.is_contiguous():
+        raise ValueError(f"bilstm_ragged_fwd: W_hh must be a contiguous fp32 (8H, H) = ({8 * H}, {H}) tensor")
+    lens.check("bilstm_ragged_fwd", B, T, xproj)
+    want_h16 = (_COMPUTE == BF16) if want_h16 is None else bool(want_h16)
+    if not (want_h32 or want_h16):
+        raise ValueError("bilstm_ragged_fwd: nothing to compute (want_h32 and want_h16 are both off)")
+    dev = xproj.device
+    h = torch.empty(B * T, 2 * H, device=dev) if want_h32 else None
+    h16 = torch.empty(B * T, 2 * H, device=dev, dtype=torch.bfloat16) if want_h16 else None
+    L.call("avc_bilstm_ragged_fwd", xproj.data_ptr(), w_hh.data_ptr(), lens.host, lens.dev.data_ptr(), B, T, H,
+           _ptr(h), _ptr(h16), _COMPUTE, stream())
+    return attach_twin(h, h16) if want_h32 else h16

@@ -477,7 +477,7 @@ def conv_dgrad(dy, B, T_in, T_out, w, pad, Wd, n_dx=None):
 
 
 # =============================================================================== conv + BN
-_PER_UTT = {"on": False}
+_PER_UTT = {"on": False, "lens": None}
 
 
 class per_utterance_bn:
@@ -488,18 +488,39 @@ class per_utterance_bn:
     with gradients enabled raises, and so does a train-mode layer reached with them enabled.  The running
     statistics and num_batches_tracked are not touched (a conversion does not change the model), and no
     BN-backward link state (BnbLink) is recorded.  Eval-mode BatchNorm is per-row independent already and
-    keeps its path; outside the context nothing changes."""
+    keeps its path; outside the context nothing changes.
+
+    lens (a kernels.Lens, default None: equal-length rows, exactly as above): the batch is ragged --
+    utterance b owns rows 0 .. lens[b] - 1 of its T-row block and the rest is padding.  Row block b is then
+    the B = 1 forward of utterance b at T = lens[b], provided the input mel is zero in the padding rows:
+    every activation that feeds a conv is kept at exactly 0.0 there, so a 5-tap 'same' conv sees past the
+    utterance's end what it sees at B = 1.  A train-mode conv + BN layer takes K.bn_seg_ragged (statistics
+    over the utterance's own rows, zeros written past them), an eval-mode one masks its output
+    (K.row_mask); the encoder's first conv takes the concat form with its input masked (the fold's edge
+    classes sit at T, not at lens[b]); a bidirectional LSTM takes K.bilstm_ragged_fwd (the backward
+    direction starts at frame lens[b] - 1); the causal LSTMs and the linear layer keep their kernels and
+    have their outputs masked.  AutoVC's layers only (convert.convert_whole checks the family)."""
+
+    def __init__(self, lens=None):
+        if lens is not None and not isinstance(lens, K.Lens):
+            raise TypeError(f"per_utterance_bn: lens must be a kernels.Lens, got {type(lens).__name__}")
+        self.lens = lens
 
     def __enter__(self):
         if torch.is_grad_enabled():
             raise RuntimeError("per_utterance_bn is forward-only: enter it under torch.no_grad()")
-        self.prev = _PER_UTT["on"]
-        _PER_UTT["on"] = True
+        self.prev = (_PER_UTT["on"], _PER_UTT["lens"])
+        _PER_UTT["on"], _PER_UTT["lens"] = True, self.lens
         return self
 
     def __exit__(self, *exc):
-        _PER_UTT["on"] = self.prev
+        _PER_UTT["on"], _PER_UTT["lens"] = self.prev
         return False
+
+
+def ragged_lens():
+    """The lengths of the ragged batch in flight (per_utterance_bn(lens=...)), or None."""
+    return _PER_UTT["lens"] if _PER_UTT["on"] else None
 
 
 def _per_utt_guard(core):
@@ -553,8 +574,14 @@ class ConvBNCore:
             # so the statistics do not come from rounded values; no epilogue partials, no finalize
             y = torch.empty(M, Co, device=dev, dtype=torch.float32)
             K.gemm(M, Co, Kdim, xop, wop, y, bias=conv.bias, row_bias=row_bias)
-            a = K.bn_seg_apply(y, M // T_out, T_out, bn.weight, bn.bias, bn.eps, self.act, residual,
-                               out_bf16=out_bf16 and bf and residual is None)
+            lens = _PER_UTT["lens"]
+            if lens is not None:
+                lens.check("conv_bn (ragged)", M // T_out, T_out, y)
+                a = K.bn_seg_ragged(y, lens, bn.weight, bn.bias, bn.eps, self.act, residual,
+                                    out_bf16=out_bf16 and bf and residual is None)
+            else:
+                a = K.bn_seg_apply(y, M // T_out, T_out, bn.weight, bn.bias, bn.eps, self.act, residual,
+                                   out_bf16=out_bf16 and bf and residual is None)
             return a, (y, None, None, T_out)
         y = torch.empty(M, Co, device=dev, dtype=torch.bfloat16 if bf else torch.float32)
         a = None
@@ -573,6 +600,10 @@ class ConvBNCore:
         mean, rstd, scale, shift = stats
         if a is None:
             a = K.bn_apply(y, scale, shift, self.act, residual, out_bf16=out_bf16 and bf and residual is None)
+        lens = ragged_lens()
+        if lens is not None:  # an eval-mode layer of a ragged batch: act(shift) and the residual leave the padding rows
+            lens.check("conv_bn (ragged)", M // T_out, T_out, a)
+            K.row_mask(a, lens)
         return a, (y, mean, rstd, T_out)
 
     def bn_grad(self, dA, saved, self_link=None):
@@ -764,6 +795,10 @@ class _EncConv0Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mel2d, emb, core, B, T, out_bf16, w, b, gamma, beta):
         x = K.enc_concat(mel2d, emb, B, T)
+        lens = ragged_lens()
+        if lens is not None:  # the broadcast speaker columns (and the mel) are zero past each utterance's end
+            lens.check("enc_conv0 (ragged)", B, T, x)
+            K.row_mask(x, lens)
         a, saved = core.forward(x, B, T, None, out_bf16)
         ctx.core, ctx.B, ctx.T, ctx.saved, ctx.n_mel = core, B, T, saved, mel2d.shape[1]
         ctx.save_for_backward(x, a)
@@ -889,7 +924,9 @@ def enc_conv0(core, mel2d, emb, B, T, out_bf16=False):
     c, bn = core.conv, core.bn
     _per_utt_guard(core)
     Kw = c.weight.shape[2]
-    if _FOLD and Kw == 2 * core.pad + 1 and T > 2 * core.pad and c.weight.shape[1] > mel2d.shape[1]:
+    # (a ragged batch takes the concat form: the fold's trailing edge classes are those of rows T - 2 and
+    # T - 1 of the block, an utterance's own last frames sit at lens[b] - 2 and lens[b] - 1)
+    if ragged_lens() is None and _FOLD and Kw == 2 * core.pad + 1 and T > 2 * core.pad and c.weight.shape[1] > mel2d.shape[1]:
         return _EncConv0FoldFn.apply(mel2d, emb, core, B, T, out_bf16, c.weight, c.bias, bn.weight, bn.bias)
     return _EncConv0Fn.apply(mel2d, emb, core, B, T, out_bf16, c.weight, c.bias, bn.weight, bn.bias)
 
@@ -1115,12 +1152,41 @@ _PAIR_OFF = bool(os.environ.get("AVC_LSTM2_OFF"))
 _PAIR_BWD = os.environ.get("AVC_LSTM2_BWD", "1") != "0"
 
 
-def lstm(mod, cores, x, B, T):
+def _lstm_ragged(cores, x, B, T, lens):
+    """lstm() for a ragged batch (per_utterance_bn(lens=...), forward only).  Bidirectional layers (the
+    encoder's, H <= 64) run K.bilstm_ragged_fwd: nothing kept for a backward, the backward direction from
+    each utterance's own last frame, zeros in the padding rows.  Unidirectional layers are causal -- frames
+    before lens[b] do not depend on later ones -- and keep their kernels; their output is masked."""
+    lens.check("lstm (ragged)", B, T, x)
+    if all(c.dirs == 2 for c in cores):
+        for core in cores:
+            if core.H > 64:
+                raise NotImplementedError(f"ragged bidirectional LSTM: H = {core.H} > 64 has no kernel")
+            wih, bsum, whh, _, _ = core.packs()
+            In = x.shape[1]
+            x = K.twin(x)
+            xproj = torch.empty(B * T, 8 * core.H, device=x.device)
+            K.gemm(B * T, 8 * core.H, In, operand(x, In), operand(wih, In), xproj, bias=bsum)
+            x = K.bilstm_ragged_fwd(xproj, whh, lens, core.H)
+        return x
+    if any(c.dirs == 2 for c in cores):
+        raise NotImplementedError("ragged LSTM: a stack that mixes directions")
+    return K.row_mask(_lstm_dense(cores, x, B, T), lens)
+
+
+def _lstm_dense(cores, x, B, T):
     if _pair_ok(cores, x, B):
         return _LSTMPairFn.apply(x, cores[0], cores[1], B, T, *cores[0].params(), *cores[1].params())
     for core in cores:
         x = _LSTMLayerFn.apply(x, core, B, T, *core.params())
     return x
+
+
+def lstm(mod, cores, x, B, T):
+    lens = ragged_lens()
+    if lens is not None:
+        return _lstm_ragged(cores, x, B, T, lens)
+    return _lstm_dense(cores, x, B, T)
 
 
 class _LSTM1FoldFn(torch.autograd.Function):
@@ -1249,7 +1315,12 @@ class _LSTM1FoldFn(torch.autograd.Function):
 def lstm1_folded(mod, core, codes, emb, B, T, nc, cd, hook=None):
     """Decoder lstm1 over cat(code expansion, emb) with the per-code / per-utterance input
     projection (see _LSTM1FoldFn); h (B*T, H)."""
-    return _LSTM1FoldFn.apply(codes, emb, core, B, T, nc, cd, hook, *core.params())
+    h = _LSTM1FoldFn.apply(codes, emb, core, B, T, nc, cd, hook, *core.params())
+    lens = ragged_lens()
+    if lens is not None:  # causal: only the padding rows (fed by the decoder convs next) need clearing
+        lens.check("lstm1_folded (ragged)", B, T, h)
+        K.row_mask(h, lens)
+    return h
 
 
 # =============================================================================== linear
@@ -1331,7 +1402,13 @@ class _LinearFn(torch.autograd.Function):
 
 
 def linear(x, w, b, cache):
-    return _LinearFn.apply(x, w, b, cache)
+    y = _LinearFn.apply(x, w, b, cache)
+    lens = ragged_lens()
+    if lens is not None:  # the bias alone makes the padding rows non-zero; y and its bf16 twin feed the postnet
+        if y.shape[0] != lens.B * lens.T:
+            raise ValueError(f"linear (ragged): {y.shape[0]} rows, the batch has B*T = {lens.B * lens.T}")
+        K.row_mask(y, lens)
+    return y
 
 
 # =============================================================================== glue
