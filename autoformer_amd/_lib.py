@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # AVC_LIB_PATH: another build of the same ABI (same-box A/B timing of two builds, tools/ only)
 LIB_PATH = os.environ.get("AVC_LIB_PATH") or os.path.join(HERE, "libautovc_hip.so")
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip", "ragged.hip"]
+SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip", "ragged.hip", "melgan_ragged.hip"]
 ABI_VERSION = 31
 
 F32, BF16 = 0, 1
@@ -267,6 +267,17 @@ _SIGS_RAGGED = {
                                       c_int, c_void_p]),
 }
 
+# The ragged-batch MelGAN glue of include/autovc_hip_vocoder.h: an eighth header and an eighth table, added the
+# same way (no ABI bump; the first seven tables are as they were); lib() binds all eight.
+_SIGS_VOCODER = {
+    "avc_mg_gather_ragged": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int_p,
+                                     c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "avc_mg_act_ragged": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_int_p, c_void_p, c_int, c_void_p, c_void_p,
+                                  c_void_p]),
+    "avc_mg_conv_out_ragged": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int_p,
+                                       c_void_p, c_int, c_void_p, c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -283,7 +294,8 @@ def build(verbose: bool = False, force: bool = False) -> str:
                                                                         "autovc_hip_audio.h",
                                                                         "autovc_hip_resample.h",
                                                                         "autovc_hip_eval.h", "autovc_hip_seg.h",
-                                                                        "autovc_hip_ragged.h")]
+                                                                        "autovc_hip_ragged.h",
+                                                                        "autovc_hip_vocoder.h")]
         newest = max(os.path.getmtime(p) for p in deps)
         if os.path.getmtime(LIB_PATH) >= newest:
             return LIB_PATH
@@ -321,7 +333,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_DV.items()) + list(_SIGS_AUDIO.items())
                                   + list(_SIGS_RESAMPLE.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_SEG.items())
-                                  + list(_SIGS_RAGGED.items())):
+                                  + list(_SIGS_RAGGED.items()) + list(_SIGS_VOCODER.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -387,3 +399,8 @@ def exported_symbols_seg():
 def exported_symbols_ragged():
     """The entry points of include/autovc_hip_ragged.h (ragged batches of whole utterances)."""
     return list(_SIGS_RAGGED.keys())
+
+
+def exported_symbols_vocoder():
+    """The entry points of include/autovc_hip_vocoder.h (the MelGAN generator over ragged batches)."""
+    return list(_SIGS_VOCODER.keys())

@@ -192,9 +192,15 @@ def _emb_rows(e, n, what):
 
 
 @torch.no_grad()
-def convert_whole(model, mels, emb_org, emb_trg, max_batch=64, max_frames=MAX_FRAMES, device=None):
+def convert_whole(model, mels, emb_org, emb_trg, max_batch=64, max_frames=MAX_FRAMES, device=None, vocoder=None):
     """Whole-utterance conversion of N utterances of any lengths: [(T_i, 80) float32 host mels] in input
     order.  mels: N host mels (T_i, 80); emb_org / emb_trg: (N, E), or (E,) for all of them.
+
+    vocoder (a melgan.MelVocoder): every batch's mel_postnet goes on to the generator where it lies, on the
+    device, as one ragged batch with the TRUE lengths T_i (MelVocoder.inverse_batch_ragged: the pad frames
+    up to P_i are not vocoded); the result is then (mels, wavs), wavs[i] a float32 host array of T_i * 256
+    samples.  Every T_i must be >= 4 then (the generator's ReflectionPad1d(3)); a batch of more than
+    melgan.VOCODER_MAX_FRAMES frames is vocoded in slices of it.
 
     Utterance i is zero-padded at the end to P_i = ceil(T_i / freq) * freq frames (crop_mel's rule); its
     result is mel_postnet of the model's B = 1 forward at T = P_i, cut back to T_i rows.  The pad frames
@@ -216,10 +222,17 @@ def convert_whole(model, mels, emb_org, emb_trg, max_batch=64, max_frames=MAX_FR
     if freq < 2:
         raise ValueError(f"convert_whole needs freq >= 2 (per-utterance statistics need two frames), got {freq}")
     plan = plan_whole([m.shape[0] for m in mels], freq, max_batch, max_frames)
+    if vocoder is not None:
+        from .melgan import VOCODER_MAX_FRAMES
+
+        short = [i for i, m in enumerate(mels) if m.shape[0] <= 3]
+        if short:  # before any launch
+            raise ValueError(f"convert_whole(vocoder=...): mels{short} have fewer than 4 frames; the generator's "
+                             "ReflectionPad1d(3) needs at least 4")
     if device is None:
         device = next(model.parameters()).device
     device = torch.device(device)
-    out = [None] * n
+    out, wavs = [None] * n, [None] * n
     for idx, Tmax in plan:
         x = np.zeros((len(idx), Tmax, 80), dtype=np.float32)
         for r, i in enumerate(idx):
@@ -228,12 +241,26 @@ def convert_whole(model, mels, emb_org, emb_trg, max_batch=64, max_frames=MAX_FR
         xd = torch.from_numpy(x).to(device)
         with Lyr.per_utterance_bn(lens=lens):
             _, psnt, _ = model(xd, torch.from_numpy(eo[idx]).to(device), torch.from_numpy(et[idx]).to(device))
-        psnt = psnt.squeeze(1).float().cpu().numpy()
+        psnt = psnt.squeeze(1).float()
+        if vocoder is not None:
+            # rows are sorted by padded length: slices of them, each cut to its own longest TRUE length
+            true = [mels[i].shape[0] for i in idx]
+            r0 = 0
+            while r0 < len(idx):
+                r1, Tm = r0 + 1, true[r0]
+                while r1 < len(idx) and (r1 + 1 - r0) * max(Tm, true[r1]) <= VOCODER_MAX_FRAMES:
+                    Tm = max(Tm, true[r1])
+                    r1 += 1
+                wav = vocoder.inverse_batch_ragged(psnt[r0:r1, :Tm], true[r0:r1]).float().cpu().numpy()
+                for r in range(r0, r1):
+                    wavs[idx[r]] = np.ascontiguousarray(wav[r - r0, :true[r] * 256])
+                r0 = r1
+        psnt = psnt.cpu().numpy()
         for r, i in enumerate(idx):
             out[i] = np.ascontiguousarray(psnt[r, :mels[i].shape[0]])
     if device.type == "cuda":
         K.check_faults(device)
-    return out
+    return out if vocoder is None else (out, wavs)
 
 
 # ----------------------------------------------------------------------------- CLI
@@ -341,14 +368,13 @@ def main(argv=None):
     org_mels = _wav_mels(list(args.src_ref), a2m, args.device, args.resample) if args.src_ref else src_mels
     e_trg = speaker_dvector(embedder, ref_mels)
     e_org = speaker_dvector(embedder, org_mels)
-    trans = convert_whole(model, src_mels, e_org, e_trg, args.max_batch, device=args.device)
+    # conversion and vocoder batch by batch on the device: each batch's mels go on to the generator as a ragged batch
+    trans, wavs = convert_whole(model, src_mels, e_org, e_trg, args.max_batch, device=args.device, vocoder=vocoder)
     os.makedirs(args.out_dir, exist_ok=True)
-    with torch.no_grad():
-        for name, mel in zip(names, trans):  # one utterance at a time: the vocoder is not batched over ragged lengths
-            wav = vocoder.inverse_frames(torch.from_numpy(mel).unsqueeze(0).to(args.device))
-            write_wav(os.path.join(args.out_dir, name + ".wav"), wav[0].float().cpu().numpy())
-            if args.save_mel:
-                np.save(os.path.join(args.out_dir, name + ".npy"), mel)
+    for name, mel, wav in zip(names, trans, wavs):
+        write_wav(os.path.join(args.out_dir, name + ".wav"), wav)
+        if args.save_mel:
+            np.save(os.path.join(args.out_dir, name + ".npy"), mel)
     print(f"{args.out_dir}: {len(trans)} wavs, {sum(m.shape[0] for m in trans)} frames")
     return 0
 

@@ -399,23 +399,33 @@ def export_grid_wavs(vocoder, mels, pads, pairs, speakers, wav_dir, len_crop, ma
     """generate.ipynb cell 8: <wav_dir>/<source speaker>/<source_id>_<target_id>.wav for every pair,
     the padded tail of the mel cut before vocoding (the isPlay=True call).  The vocoder runs batched
     over mels of equal length (MelVocoder.inverse_frames).  len_crop None: every mel at its own full length
-    (the --whole export; pads is ignored)."""
+    (the --whole export; pads is ignored), all pairs planned together into ragged batches
+    (MelVocoder.inverse_ragged)."""
+    written = []
+
+    def write(i, wav):
+        s, t = pairs[i]
+        folder = os.path.join(wav_dir, str(speakers[s]))
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, f"{s}_{t}.wav")
+        write_wav(path, wav)
+        written.append(path)
+
+    if len_crop is None:
+        n = len(pads)
+        for i, wav in enumerate(vocoder.inverse_ragged([mels[i] for i in range(n)], max_batch=max_batch)):
+            write(i, wav.float().cpu().numpy())
+        return written
     by_len = {}
     for i, pad in enumerate(pads):
-        by_len.setdefault(mels[i].shape[0] if len_crop is None else len_crop - pad, []).append(i)
-    written = []
+        by_len.setdefault(len_crop - pad, []).append(i)
     for T, idx in sorted(by_len.items()):
         for k in range(0, len(idx), max_batch):
             part = idx[k:k + max_batch]
             x = torch.from_numpy(np.stack([mels[i][:T] for i in part])).to(vocoder.device)
             wav = vocoder.inverse_frames(x).float().cpu().numpy()
             for r, i in enumerate(part):
-                s, t = pairs[i]
-                folder = os.path.join(wav_dir, str(speakers[s]))
-                os.makedirs(folder, exist_ok=True)
-                path = os.path.join(folder, f"{s}_{t}.wav")
-                write_wav(path, wav[r])
-                written.append(path)
+                write(i, wav[r])
     return written
 
 

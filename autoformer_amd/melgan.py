@@ -21,6 +21,11 @@ Weight norm (g v / ||v||) is folded into the packed GEMM operands once per param
 (inference weights do not change between calls).  There is no CPU or torch fallback: the
 kernels raise on host tensors.
 
+`Generator.frames_ragged` / `MelVocoder.inverse_ragged` run the same sequence over utterances of
+different lengths in one batch: mg_gather, the LeakyReLU twin in front of each upsampler and
+mg_conv_out take the length-aware forms of melgan_ragged.hip (include/autovc_hip_vocoder.h), the
+GEMMs are the same calls.
+
 The other direction, waveform -> log-mel (reference modules.py:26-69 `Audio2Mel`, interface.py:33-41
 `MelVocoder.__call__`), is `Audio2Mel` below: one fused fp32 kernel (audio.hip) behind the
 reference's constructor and buffers, with the Slaney filterbank as a closed form.
@@ -160,21 +165,71 @@ class Generator(nn.Module):
         K.gemm(M, N, Kd, a, K.operand(w, Kd), y, bias=bias, accumulate=accumulate, c_bf16=y16 if bf else None)
         return K.attach_twin(y, y16) if bf and out is None else y
 
-    def _gather(self, x, B, Lf, C, taps, dil, pad, act):
+    # The three kernels that look across rows.  lens None: the rectangular forms (melgan.hip), every row
+    # of the (B, Lf) block an utterance's own.  lens a kernels.Lens of MEL-frame counts: the length-aware
+    # forms (melgan_ragged.hip) at this stage's cumulative upsampling `scale` (Lf = lens.T * scale).
+    def _gather(self, x, B, Lf, C, taps, dil, pad, act, lens=None, scale=1):
         src = getattr(x, "_bf16", None)
         src = x if src is None else src
         Lo = Lf + 2 * pad - dil * (taps - 1)
         out = torch.empty(B * Lo, taps * C, device=x.device, dtype=K.compute_torch_dtype())
-        L.call("avc_mg_gather", src.data_ptr(), K._dt(src), B, Lf, C, taps, dil, pad, 1, int(act), SLOPE,
-               out.data_ptr(), K._dt(out), K.stream())
+        if lens is None:
+            L.call("avc_mg_gather", src.data_ptr(), K._dt(src), B, Lf, C, taps, dil, pad, 1, int(act), SLOPE,
+                   out.data_ptr(), K._dt(out), K.stream())
+        else:
+            L.call("avc_mg_gather_ragged", src.data_ptr(), K._dt(src), B, lens.T, C, taps, dil, pad, int(act), SLOPE,
+                   lens.host, lens.dev.data_ptr(), scale, out.data_ptr(), K._dt(out), K.stream())
         return out
 
-    def _act(self, x):
+    def _act(self, x, B=None, C=None, lens=None, scale=1):
         out = torch.empty(x.shape, device=x.device, dtype=K.compute_torch_dtype())
         bf = out.dtype == torch.bfloat16
-        L.call("avc_mg_act", x.data_ptr(), x.numel(), SLOPE, None if bf else out.data_ptr(),
-               out.data_ptr() if bf else None, K.stream())
+        o32, o16 = (None, out.data_ptr()) if bf else (out.data_ptr(), None)
+        if lens is None:
+            L.call("avc_mg_act", x.data_ptr(), x.numel(), SLOPE, o32, o16, K.stream())
+        else:
+            L.call("avc_mg_act_ragged", x.data_ptr(), B, lens.T, C, SLOPE, lens.host, lens.dev.data_ptr(), scale, o32,
+                   o16, K.stream())
         return out
+
+    def _run(self, x, B, T, lens):
+        """The launch sequence of frames (lens None) and frames_ragged (lens a kernels.Lens, T = lens.T)."""
+        P = self.packs()
+        m = self.model
+        Lf, u = T, 1  # rows per utterance block at this stage, cumulative upsampling
+        C = m[1].weight_v.shape[0]
+        w, b = P["in"]
+        g = self._gather(x.contiguous(), B, Lf, self.input_size, 7, 1, 3, act=False, lens=lens, scale=u)
+        y = self._gemm(B * Lf, C, 7 * self.input_size, K.operand(g, 7 * self.input_size), w, b)
+        for r, ct, blocks in self._stages:
+            Cin, Cout = C, m[ct].weight_v.shape[1]
+            w, b = P[ct]
+            # LeakyReLU before the upsampler (modules.py:99).  Ragged: zeros past each utterance's last row, so
+            # the zero-padded 3-tap window below reads after it what it reads at the block edge (and at B = 1)
+            a = self._act(y, B, Cin, lens, u)
+            y = self._gemm(B * Lf, r * Cout, 3 * Cin, K.operand(a, Cin, window=(3, 1, Lf, Lf, Cin)), w, b)
+            Lf, C, u = Lf * r, Cout, u * r
+            y16 = getattr(y, "_bf16", None)  # a view is a new tensor: carry the twin over
+            y = K.attach_twin(y.view(B * Lf, C), None if y16 is None else y16.view(B * Lf, C))
+            for bi in blocks:
+                (w1, b1), (w2, b2), (ws, bs) = P[bi]
+                d = m[bi].dilation
+                h = self._gather(y, B, Lf, C, 3, d, d, act=True, lens=lens, scale=u)
+                h1 = self._gemm(B * Lf, C, 3 * C, K.operand(h, 3 * C), w1, b1)
+                # the rectangular twin in the ragged case too: it feeds the 1x1 GEMM, which is row-wise, so a
+                # padding row of h2 reaches padding rows only (finite there: GEMM outputs of zeros and biases)
+                h2 = self._act(h1)
+                out = self._gemm(B * Lf, C, C, K.operand(y, C), ws, bs)  # shortcut (modules.py:83-86)
+                y = self._gemm(B * Lf, C, C, K.operand(h2, C), w2, b2, out=out, accumulate=True)
+        wo, bo = P["out"]
+        audio = torch.empty(B * Lf, device=x.device)
+        if lens is None:
+            L.call("avc_mg_conv_out", y.data_ptr(), B, Lf, C, 7, wo.data_ptr(), bo.data_ptr(), SLOPE,
+                   audio.data_ptr(), K.stream())
+        else:
+            L.call("avc_mg_conv_out_ragged", y.data_ptr(), B, lens.T, C, 7, wo.data_ptr(), bo.data_ptr(), SLOPE,
+                   lens.host, lens.dev.data_ptr(), u, audio.data_ptr(), K.stream())
+        return audio.view(B, Lf)
 
     @torch.no_grad()
     def frames(self, x, B, T):
@@ -185,34 +240,26 @@ class Generator(nn.Module):
                              f"{tuple(x.shape)} {x.dtype}")
         if T <= 3:
             raise ValueError("Generator: ReflectionPad1d(3) needs at least 4 mel frames (modules.py:95)")
-        P = self.packs()
-        m = self.model
-        Lf = T
-        C = m[1].weight_v.shape[0]
-        w, b = P["in"]
-        g = self._gather(x.contiguous(), B, Lf, self.input_size, 7, 1, 3, act=False)
-        y = self._gemm(B * Lf, C, 7 * self.input_size, K.operand(g, 7 * self.input_size), w, b)
-        for r, ct, blocks in self._stages:
-            Cin, Cout = C, m[ct].weight_v.shape[1]
-            w, b = P[ct]
-            a = self._act(y)  # LeakyReLU before the upsampler (modules.py:99)
-            y = self._gemm(B * Lf, r * Cout, 3 * Cin, K.operand(a, Cin, window=(3, 1, Lf, Lf, Cin)), w, b)
-            Lf, C = Lf * r, Cout
-            y16 = getattr(y, "_bf16", None)  # a view is a new tensor: carry the twin over
-            y = K.attach_twin(y.view(B * Lf, C), None if y16 is None else y16.view(B * Lf, C))
-            for bi in blocks:
-                (w1, b1), (w2, b2), (ws, bs) = P[bi]
-                d = m[bi].dilation
-                h = self._gather(y, B, Lf, C, 3, d, d, act=True)
-                h1 = self._gemm(B * Lf, C, 3 * C, K.operand(h, 3 * C), w1, b1)
-                h2 = self._act(h1)
-                out = self._gemm(B * Lf, C, C, K.operand(y, C), ws, bs)  # shortcut (modules.py:83-86)
-                y = self._gemm(B * Lf, C, C, K.operand(h2, C), w2, b2, out=out, accumulate=True)
-        wo, bo = P["out"]
-        audio = torch.empty(B * Lf, device=x.device)
-        L.call("avc_mg_conv_out", y.data_ptr(), B, Lf, C, 7, wo.data_ptr(), bo.data_ptr(), SLOPE, audio.data_ptr(),
-               K.stream())
-        return audio.view(B, Lf)
+        return self._run(x, B, T, None)
+
+    @torch.no_grad()
+    def frames_ragged(self, x, lens):
+        """A batch of utterances of different lengths.  x: frame-major mel (B*Tmax, input_size) fp32 on the
+        device, utterance b in rows b*Tmax .. b*Tmax + lens[b] - 1; lens: a kernels.Lens (B lengths, T =
+        Tmax).  -> audio (B, Tmax*hop) fp32: audio[b, :lens[b]*hop] is frames(mel_b, 1, lens[b]), the samples
+        after it are exactly 0.0.  The rows of x past an utterance's end are never read."""
+        K._dev(x)
+        if not isinstance(lens, K.Lens):
+            raise TypeError("Generator.frames_ragged: lens must be a kernels.Lens")
+        B, T = lens.B, lens.T
+        if x.dtype != torch.float32 or x.shape != (B * T, self.input_size):
+            raise ValueError(f"Generator.frames_ragged: expected fp32 ({B * T}, {self.input_size}), got "
+                             f"{tuple(x.shape)} {x.dtype}")
+        lens.check("Generator.frames_ragged", B, T, x)
+        if min(lens.vals) <= 3:
+            raise ValueError(f"Generator: ReflectionPad1d(3) needs at least 4 mel frames per utterance "
+                             f"(modules.py:95), got lengths {list(lens.vals)}")
+        return self._run(x, B, T, lens)
 
     @torch.no_grad()
     def forward(self, x):
@@ -391,6 +438,18 @@ class Audio2Mel(nn.Module):
         return self._run(audio.float().squeeze(1), None, None, L.MEL_CHANNEL_MAJOR)
 
 
+# Mel frames (B * Tmax) one ragged vocoder batch may hold.  Per mel frame a stage of cumulative upsampling u
+# and width C holds u*C elements per tensor: 2048 after the first upsampler (8 x 256), then 8192 at each of
+# the three widest stages (64 x 128, 128 x 64, 256 x 32).  Inside a residual block of those stages five tensors
+# are alive at once -- y, the 3-tap gather h (3 C wide), h1, its LeakyReLU twin h2 and the shortcut / sum -- at
+# 6 + 6 + 6 + 2 + 6 = 26 B per element in bf16 mode (fp32 plus bf16 twin for the GEMM outputs, bf16 operands)
+# and 4 + 12 + 4 + 4 + 4 = 28 B in fp32 mode: 28 x 8192 = 224 KiB per mel frame.  8192 frames keep the live
+# set at 1.75 GiB (64 utterances of 128 frames, or 12 of the longest the bench draws); the GEMMs are past
+# filling the chip long before that (B = 16 x 176 frames already is).
+VOCODER_MAX_FRAMES = 8192
+VOCODER_MAX_BATCH = 32
+
+
 class MelVocoder:
     """melgan/interface.py:23-53: `inverse(mel (B, 80, T)) -> (B, T*256)` on the HIP generator and
     `__call__(audio (B, L)) -> (B, 80, T)` on the HIP Audio2Mel.  The checkpoint is read with
@@ -416,6 +475,44 @@ class MelVocoder:
         """(B, T, 80) frame-major mel (the Converter's output layout) -> (B, T*256): no transpose."""
         B, T, C = mel_frames.shape
         return self.mel2wav.frames(mel_frames.reshape(B * T, C).float().contiguous(), B, T)
+
+    def inverse_batch_ragged(self, mel_frames, lens):
+        """One ragged batch that is already on the device: (B, Tmax, 80) frame-major mel, utterance b valid in
+        its first lens[b] frames (the rest is never read) -> (B, Tmax*256), zeros after sample lens[b]*256."""
+        B, T, C = mel_frames.shape
+        return self.mel2wav.frames_ragged(mel_frames.reshape(B * T, C).float().contiguous(),
+                                          K.Lens(lens, T, mel_frames.device))
+
+    def inverse_ragged(self, mels, max_batch=VOCODER_MAX_BATCH, max_frames=VOCODER_MAX_FRAMES):
+        """Mels of any lengths -> their waveforms, in input order.  mels: a list of (T_i >= 4, 80) host arrays
+        or device tensors; returns a list of 1-D fp32 device tensors of T_i * 256 samples, each the B = 1
+        forward of its mel at its own length.  Batches: convert.plan_whole with freq = 1 (sorted by length, cut
+        at B <= max_batch and B * Tmax <= max_frames)."""
+        from .convert import plan_whole
+
+        mels = list(mels)
+        for i, m in enumerate(mels):
+            if len(m.shape) != 2 or m.shape[1] != 80:
+                raise ValueError(f"inverse_ragged: mels[{i}] must be (T, 80), got {tuple(m.shape)}")
+            if m.shape[0] <= 3:  # before any launch: a later batch must not run ahead of the refusal
+                raise ValueError(f"inverse_ragged: mels[{i}] has {m.shape[0]} frames; ReflectionPad1d(3) needs at "
+                                 "least 4 (modules.py:95)")
+        lens = [int(m.shape[0]) for m in mels]
+        out = [None] * len(mels)
+        for idx, Tmax in plan_whole(lens, 1, max_batch, max_frames):
+            if all(isinstance(mels[i], np.ndarray) for i in idx):  # one upload per batch
+                host = np.zeros((len(idx), Tmax, 80), dtype=np.float32)
+                for r, i in enumerate(idx):
+                    host[r, :lens[i]] = mels[i]
+                x = torch.from_numpy(host).to(self.device)
+            else:
+                x = torch.zeros(len(idx), Tmax, 80, device=self.device)
+                for r, i in enumerate(idx):
+                    x[r, :lens[i]] = torch.as_tensor(mels[i]).to(self.device, torch.float32)
+            audio = self.inverse_batch_ragged(x, [lens[i] for i in idx])
+            for r, i in enumerate(idx):
+                out[i] = audio[r, :lens[i] * self.mel2wav.hop_length]
+        return out
 
 
 def load_model(mel2wav_path, device="cuda:0"):
