@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # AVC_LIB_PATH: another build of the same ABI (same-box A/B timing of two builds, tools/ only)
 LIB_PATH = os.environ.get("AVC_LIB_PATH") or os.path.join(HERE, "libautovc_hip.so")
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip", "ragged.hip", "melgan_ragged.hip"]
+SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip", "ragged.hip", "melgan_ragged.hip", "ge2e.hip"]
 ABI_VERSION = 31
 
 F32, BF16 = 0, 1
@@ -278,6 +278,14 @@ _SIGS_VOCODER = {
                                        c_void_p, c_int, c_void_p, c_void_p]),
 }
 
+# The GE2E loss of include/autovc_hip_ge2e.h: a ninth header and a ninth table, added the same way (no ABI
+# bump; the first eight tables are as they were); lib() binds all nine.
+GE2E_MAX_N, GE2E_MAX_M, GE2E_MAX_D, GE2E_MAX_ROWS = 1024, 1024, 2048, 8192
+_SIGS_GE2E = {
+    "avc_ge2e_ws": (c_size, [c_int, c_int, c_int]),
+    "avc_ge2e": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -295,7 +303,8 @@ def build(verbose: bool = False, force: bool = False) -> str:
                                                                         "autovc_hip_resample.h",
                                                                         "autovc_hip_eval.h", "autovc_hip_seg.h",
                                                                         "autovc_hip_ragged.h",
-                                                                        "autovc_hip_vocoder.h")]
+                                                                        "autovc_hip_vocoder.h",
+                                                                        "autovc_hip_ge2e.h")]
         newest = max(os.path.getmtime(p) for p in deps)
         if os.path.getmtime(LIB_PATH) >= newest:
             return LIB_PATH
@@ -333,7 +342,8 @@ def lib():
         L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_DV.items()) + list(_SIGS_AUDIO.items())
                                   + list(_SIGS_RESAMPLE.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_SEG.items())
-                                  + list(_SIGS_RAGGED.items()) + list(_SIGS_VOCODER.items())):
+                                  + list(_SIGS_RAGGED.items()) + list(_SIGS_VOCODER.items())
+                                  + list(_SIGS_GE2E.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -404,3 +414,8 @@ def exported_symbols_ragged():
 def exported_symbols_vocoder():
     """The entry points of include/autovc_hip_vocoder.h (the MelGAN generator over ragged batches)."""
     return list(_SIGS_VOCODER.keys())
+
+
+def exported_symbols_ge2e():
+    """The entry points of include/autovc_hip_ge2e.h (the GE2E loss and its gradients)."""
+    return list(_SIGS_GE2E.keys())

@@ -1439,3 +1439,33 @@ def bilstm_ragged_fwd(xproj, w_hh, lens: Lens, H, want_h32=True, want_h16=None):
     L.call("avc_bilstm_ragged_fwd", xproj.data_ptr(), w_hh.data_ptr(), lens.host, lens.dev.data_ptr(), B, T, H,
            _ptr(h), _ptr(h16), _COMPUTE, stream())
     return attach_twin(h, h16) if want_h32 else h16
+
+
+# ------------------------------------------------------------------------- GE2E loss
+def ge2e(e, N, M, w, grads=True):
+    """The GE2E loss of e (N, M, D) with scale w (avc_ge2e): L, and with `grads` dL/de and dL/dw for an
+    upstream gradient of 1 -- (L (), de (N*M, D) | None, dw () | None).  e: contiguous fp32 with N*M*D
+    elements (float4 accesses when D % 4 == 0 and e is 16-byte aligned, single elements otherwise);
+    w: a one-element fp32 tensor.  Deterministic: two calls on the same input are bit-identical."""
+    _dev(e, w)
+    N, M = int(N), int(M)
+    if not isinstance(e, torch.Tensor) or e.dtype != torch.float32 or not e.is_contiguous():
+        raise TypeError(f"ge2e: e must be a contiguous fp32 tensor, got {getattr(e, 'dtype', type(e))} "
+                        f"{tuple(getattr(e, 'shape', ()))}")
+    if w.dtype != torch.float32 or w.numel() != 1:
+        raise TypeError(f"ge2e: w must be a one-element fp32 tensor, got {w.dtype} {tuple(w.shape)}")
+    if N < 1 or M < 1 or e.numel() < N * M or e.numel() % (N * M):
+        raise ValueError(f"ge2e: e has {e.numel()} elements, not N*M = {N}*{M} rows of equal length")
+    D = e.numel() // (N * M)
+    nbytes = int(L.lib().avc_ge2e_ws(N, M, D))
+    if nbytes == 0:
+        raise ValueError(f"ge2e: N = {N}, M = {M}, D = {D} outside 2 <= N <= {L.GE2E_MAX_N}, 2 <= M <= {L.GE2E_MAX_M}, "
+                         f"1 <= D <= {L.GE2E_MAX_D}, N*M <= {L.GE2E_MAX_ROWS}")
+    dev = e.device
+    ws = torch.empty(nbytes // 4, device=dev)
+    loss = torch.empty((), device=dev)
+    de = torch.empty(N * M, D, device=dev) if grads else None
+    dw = torch.empty((), device=dev) if grads else None
+    L.call("avc_ge2e", e.data_ptr(), N, M, D, w.data_ptr(), loss.data_ptr(), _ptr(de), _ptr(dw), ws.data_ptr(),
+           stream())
+    return loss, de, dw
