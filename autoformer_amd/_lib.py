@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # AVC_LIB_PATH: another build of the same ABI (same-box A/B timing of two builds, tools/ only)
 LIB_PATH = os.environ.get("AVC_LIB_PATH") or os.path.join(HERE, "libautovc_hip.so")
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip", "ragged.hip", "melgan_ragged.hip", "ge2e.hip"]
+SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip", "ragged.hip", "melgan_ragged.hip", "ge2e.hip", "xent.hip"]
 ABI_VERSION = 31
 
 F32, BF16 = 0, 1
@@ -286,6 +286,15 @@ _SIGS_GE2E = {
     "avc_ge2e": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# Softmax cross-entropy of include/autovc_hip_xent.h: a tenth header and a tenth table, added the same way (no
+# ABI bump; the first nine tables are as they were); lib() binds all ten.
+XENT_MAX_B, XENT_MAX_C = 65536, 16384
+_SIGS_XENT = {
+    "avc_xent_ws": (c_size, [c_int, c_int]),
+    "avc_xent": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p,
+                         c_void_p, c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -304,7 +313,7 @@ def build(verbose: bool = False, force: bool = False) -> str:
                                                                         "autovc_hip_eval.h", "autovc_hip_seg.h",
                                                                         "autovc_hip_ragged.h",
                                                                         "autovc_hip_vocoder.h",
-                                                                        "autovc_hip_ge2e.h")]
+                                                                        "autovc_hip_ge2e.h", "autovc_hip_xent.h")]
         newest = max(os.path.getmtime(p) for p in deps)
         if os.path.getmtime(LIB_PATH) >= newest:
             return LIB_PATH
@@ -343,7 +352,7 @@ def lib():
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_DV.items()) + list(_SIGS_AUDIO.items())
                                   + list(_SIGS_RESAMPLE.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_SEG.items())
                                   + list(_SIGS_RAGGED.items()) + list(_SIGS_VOCODER.items())
-                                  + list(_SIGS_GE2E.items())):
+                                  + list(_SIGS_GE2E.items()) + list(_SIGS_XENT.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -419,3 +428,8 @@ def exported_symbols_vocoder():
 def exported_symbols_ge2e():
     """The entry points of include/autovc_hip_ge2e.h (the GE2E loss and its gradients)."""
     return list(_SIGS_GE2E.keys())
+
+
+def exported_symbols_xent():
+    """The entry points of include/autovc_hip_xent.h (softmax cross-entropy, its gradient, the top-1 count)."""
+    return list(_SIGS_XENT.keys())

@@ -1469,3 +1469,80 @@ def ge2e(e, N, M, w, grads=True):
     L.call("avc_ge2e", e.data_ptr(), N, M, D, w.data_ptr(), loss.data_ptr(), _ptr(de), _ptr(dw), ws.data_ptr(),
            stream())
     return loss, de, dw
+
+
+# ------------------------------------------------------------------------- softmax cross-entropy (autovc_hip_xent.h)
+class Labels:
+    """Class labels of B rows for C classes: host integers (a list, a numpy array or a CPU tensor), checked
+    against [0, C) here, on the host, and sent to the device as int32 (read by the kernel).  What xent takes
+    besides this is a raw int32 device tensor, which is the caller's promise that the values were checked."""
+
+    def __init__(self, values, C, device):
+        if isinstance(values, torch.Tensor):
+            if values.is_cuda:
+                raise TypeError("Labels: the values are checked on the host; pass a CPU tensor, an array or a list")
+            if values.dtype.is_floating_point or values.dtype.is_complex or values.dtype == torch.bool:
+                raise TypeError(f"Labels: integer labels, got a {values.dtype} tensor")
+            vals = values.reshape(-1).tolist()
+        elif hasattr(values, "dtype") and hasattr(values, "tolist"):  # a numpy array
+            if getattr(values.dtype, "kind", "") not in "iu":
+                raise TypeError(f"Labels: integer labels, got a {values.dtype} array")
+            vals = values.reshape(-1).tolist()
+        else:
+            vals = list(values)
+            for v in vals:
+                if isinstance(v, bool) or not hasattr(v, "__index__"):
+                    raise TypeError(f"Labels: integer labels, got {v!r}")
+            vals = [int(v) for v in vals]
+        C = int(C)
+        if not vals:
+            raise ValueError("Labels: no labels")
+        if C < 1 or min(vals) < 0 or max(vals) >= C:
+            raise ValueError(f"Labels: every label must lie in 0..C - 1 = {C - 1}, got {min(vals)}..{max(vals)}")
+        self.B, self.C, self.vals = len(vals), C, tuple(vals)
+        self.dev = torch.tensor(vals, dtype=torch.int32, device=device)
+
+
+def xent(logits, labels, smooth=0.0, grads=True):
+    """Softmax cross-entropy with label smoothing (avc_xent): (L (), dlogits (B, C) | None, correct () int32) --
+    the mean over the rows of F.cross_entropy(logits, labels, label_smoothing=smooth), with `grads` its
+    gradient for an upstream gradient of 1, and the number of rows whose largest logit is at the label.
+    logits: fp32 (B, C) with unit column stride (a row stride above C is the kernel's ld); labels: a Labels,
+    or an int32 (B,) device tensor whose values the caller has checked.  Deterministic."""
+    _dev(logits)
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.dim() != 2:
+        raise TypeError(f"xent: logits must be an fp32 (B, C) tensor, got {getattr(logits, 'dtype', type(logits))} "
+                        f"{tuple(getattr(logits, 'shape', ()))}")
+    B, C = logits.shape
+    if B < 1 or C < 1:
+        raise ValueError(f"xent: logits {tuple(logits.shape)} has no rows or no columns")
+    ld = logits.stride(0) if B > 1 else max(logits.stride(0), C)
+    if logits.stride(1) != 1 or ld < C:
+        raise ValueError(f"xent: logits must have unit column stride and a row stride of at least C, got strides "
+                         f"{tuple(logits.stride())}")
+    if isinstance(labels, Labels):
+        if labels.B != B or labels.C != C:
+            raise ValueError(f"xent: labels describe B = {labels.B}, C = {labels.C}, the logits are {B} x {C}")
+        lab = labels.dev
+    else:
+        lab = labels
+        _dev(lab)
+        if not isinstance(lab, torch.Tensor) or lab.dtype != torch.int32 or tuple(lab.shape) != (B,) \
+                or not lab.is_contiguous():
+            raise TypeError("xent: labels must be a kernels.Labels or a contiguous int32 (B,) device tensor")
+    if lab.device != logits.device:
+        raise ValueError(f"xent: the logits are on {logits.device}, the labels on {lab.device}")
+    smooth = float(smooth)
+    if not 0.0 <= smooth < 1.0:
+        raise ValueError(f"xent: smooth = {smooth} outside [0, 1)")
+    nbytes = int(L.lib().avc_xent_ws(B, C))
+    if nbytes == 0:
+        raise ValueError(f"xent: B = {B}, C = {C} outside 1 <= B <= {L.XENT_MAX_B}, 1 <= C <= {L.XENT_MAX_C}")
+    dev = logits.device
+    ws = torch.empty(nbytes // 4, device=dev)
+    loss = torch.empty((), device=dev)
+    correct = torch.empty((), device=dev, dtype=torch.int32)
+    d = torch.empty(B, C, device=dev) if grads else None
+    L.call("avc_xent", logits.data_ptr(), ld, B, C, lab.data_ptr(), smooth, loss.data_ptr(), _ptr(d), C,
+           correct.data_ptr(), ws.data_ptr(), stream())
+    return loss, d, correct

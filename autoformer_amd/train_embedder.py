@@ -112,7 +112,8 @@ class ReadAhead:
     crops of a batch overlap the device's work on the one before.  Yields host tensors (pinned where a
     device is there, so the consumer's copy can be non_blocking; each batch has a buffer of its own).
     `state` is the sampler state after the batch handed out last -- what a checkpoint must hold, not the
-    state of the sampler itself, which is `depth` draws further on.  `count` batches are produced in all."""
+    state of the sampler itself, which is `depth` draws further on.  `count` batches are produced in all.
+    A sampler that yields a tuple (x, ...) gets (tensor of x, ...) back: only x is converted and pinned."""
 
     def __init__(self, batches, count, depth=2, pin=None):
         import queue
@@ -134,8 +135,13 @@ class ReadAhead:
                 for _ in range(max(count, 0)):
                     if self._stop.is_set():
                         return
-                    x = torch.from_numpy(next(batches))
-                    put((x.pin_memory() if pin else x, batches.state()))
+                    item = next(batches)
+                    rest = ()
+                    if isinstance(item, tuple):  # (x, ...): x as below, the rest handed through as it is
+                        item, rest = item[0], item[1:]
+                    x = torch.from_numpy(item)
+                    x = x.pin_memory() if pin else x
+                    put(((x,) + rest if rest else x, batches.state()))
             except BaseException as exc:  # surface loader errors in the consumer
                 put(exc)
         self._thread = threading.Thread(target=produce, daemon=True)
