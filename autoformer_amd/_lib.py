@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # AVC_LIB_PATH: another build of the same ABI (same-box A/B timing of two builds, tools/ only)
 LIB_PATH = os.environ.get("AVC_LIB_PATH") or os.path.join(HERE, "libautovc_hip.so")
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip", "ragged.hip", "melgan_ragged.hip", "ge2e.hip", "xent.hip"]
+SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip", "ragged.hip", "melgan_ragged.hip", "ge2e.hip", "xent.hip", "critic_loss.hip"]
 ABI_VERSION = 31
 
 F32, BF16 = 0, 1
@@ -295,6 +295,18 @@ _SIGS_XENT = {
                          c_void_p, c_void_p]),
 }
 
+# The critic step's loss tail of include/autovc_hip_critic.h: an eleventh header and an eleventh table, added the
+# same way (no ABI bump; the first ten tables are as they were); lib() binds all eleven.
+CRITIC_MAX_B, CRITIC_MAX_E, CRITIC_MAX_N = 4096, 4096, 65536
+_SIGS_CRITIC = {
+    "avc_critic_loss_ws": (c_size, [c_int]),
+    "avc_critic_loss": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "avc_critic_loss_grad": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                     c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_int, c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -313,7 +325,8 @@ def build(verbose: bool = False, force: bool = False) -> str:
                                                                         "autovc_hip_eval.h", "autovc_hip_seg.h",
                                                                         "autovc_hip_ragged.h",
                                                                         "autovc_hip_vocoder.h",
-                                                                        "autovc_hip_ge2e.h", "autovc_hip_xent.h")]
+                                                                        "autovc_hip_ge2e.h", "autovc_hip_xent.h",
+                                                                        "autovc_hip_critic.h")]
         newest = max(os.path.getmtime(p) for p in deps)
         if os.path.getmtime(LIB_PATH) >= newest:
             return LIB_PATH
@@ -352,7 +365,8 @@ def lib():
         for name, (res, args) in (list(_SIGS.items()) + list(_SIGS_DV.items()) + list(_SIGS_AUDIO.items())
                                   + list(_SIGS_RESAMPLE.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_SEG.items())
                                   + list(_SIGS_RAGGED.items()) + list(_SIGS_VOCODER.items())
-                                  + list(_SIGS_GE2E.items()) + list(_SIGS_XENT.items())):
+                                  + list(_SIGS_GE2E.items()) + list(_SIGS_XENT.items())
+                                  + list(_SIGS_CRITIC.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -433,3 +447,8 @@ def exported_symbols_ge2e():
 def exported_symbols_xent():
     """The entry points of include/autovc_hip_xent.h (softmax cross-entropy, its gradient, the top-1 count)."""
     return list(_SIGS_XENT.keys())
+
+
+def exported_symbols_critic():
+    """The entry points of include/autovc_hip_critic.h (the critic step's fused loss tail and its gradients)."""
+    return list(_SIGS_CRITIC.keys())

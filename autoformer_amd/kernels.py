@@ -1546,3 +1546,67 @@ def xent(logits, labels, smooth=0.0, grads=True):
     L.call("avc_xent", logits.data_ptr(), ld, B, C, lab.data_ptr(), smooth, loss.data_ptr(), _ptr(d), C,
            correct.data_ptr(), ws.data_ptr(), stream())
     return loss, d, correct
+
+
+# ------------------------------------------------------------------------- critic loss tail (autovc_hip_critic.h)
+def _critic_args(who, e, t, p_real, p_fake):
+    """Checked (e, lde, t, ldt, B, E, p_real, n_r, p_fake, n_f) of the critic loss calls."""
+    _dev(e, t, p_real, p_fake)
+    for name, v in (("e", e), ("t", t), ("p_real", p_real), ("p_fake", p_fake)):
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float32:
+            raise TypeError(f"{who}: {name} must be an fp32 tensor, got {getattr(v, 'dtype', type(v))}")
+    if e.dim() != 2 or t.dim() != 2 or e.shape != t.shape:
+        raise ValueError(f"{who}: e and t must both be (B, E), got {tuple(e.shape)} and {tuple(t.shape)}")
+    B, E = e.shape
+    n_r, n_f = p_real.numel(), p_fake.numel()
+    if not (1 <= B <= L.CRITIC_MAX_B and 1 <= E <= L.CRITIC_MAX_E):
+        raise ValueError(f"{who}: B = {B}, E = {E} outside 1 <= B <= {L.CRITIC_MAX_B}, 1 <= E <= {L.CRITIC_MAX_E}")
+    if not (1 <= n_r <= L.CRITIC_MAX_N and 1 <= n_f <= L.CRITIC_MAX_N):
+        raise ValueError(f"{who}: n_r = {n_r}, n_f = {n_f} outside 1 <= n <= {L.CRITIC_MAX_N}")
+    lds = []
+    for name, v in (("e", e), ("t", t)):
+        ld = v.stride(0) if B > 1 else max(v.stride(0), E)
+        if (E > 1 and v.stride(1) != 1) or ld < E:
+            raise ValueError(f"{who}: {name} must have unit column stride and a row stride of at least E, got strides "
+                             f"{tuple(v.stride())}")
+        lds.append(ld)
+    if not p_real.is_contiguous() or not p_fake.is_contiguous():
+        raise ValueError(f"{who}: p_real and p_fake must be contiguous")
+    return e, lds[0], t, lds[1], B, E, p_real, n_r, p_fake, n_f
+
+
+def critic_loss(e, t, p_real, p_fake, lambda_cls, lambda_dis, base=None):
+    """The critic step's loss tail in one launch (avc_critic_loss): (out, ws) with out a (4,) device tensor
+    [c_loss, d_loss, lambda_cls c_loss + lambda_dis d_loss, base + that] -- c_loss = F.cosine_embedding_loss(e, t,
+    ones), d_loss = BCE(p_real, 1) + BCE(p_fake, 0) -- and ws what critic_loss_grad reads.  e, t: fp32 (B, E) with
+    unit column stride; base: a one-element fp32 device tensor or None.  Deterministic."""
+    e, lde, t, ldt, B, E, p_real, n_r, p_fake, n_f = _critic_args("critic_loss", e, t, p_real, p_fake)
+    if base is not None:
+        _dev(base)
+        if base.dtype != torch.float32 or base.numel() != 1:
+            raise TypeError(f"critic_loss: base must be a one-element fp32 tensor, got {base.dtype} {tuple(base.shape)}")
+    dev = e.device
+    out = torch.empty(4, device=dev)
+    ws = torch.empty(int(L.lib().avc_critic_loss_ws(B)) // 4, device=dev)
+    L.call("avc_critic_loss", e.data_ptr(), lde, t.data_ptr(), ldt, B, E, p_real.data_ptr(), n_r, p_fake.data_ptr(),
+           n_f, _ptr(base), float(lambda_cls), float(lambda_dis), out.data_ptr(), ws.data_ptr(), stream())
+    return out, ws
+
+
+def critic_loss_grad(e, t, p_real, p_fake, lambda_cls, lambda_dis, ws, d, need):
+    """Gradients of critic_loss's outputs in one launch (avc_critic_loss_grad): d = the 4 upstream device scalars of
+    out[0..3] (or None), need = (e, p_real, p_fake) flags; returns the three gradients (None where not needed)."""
+    e, lde, t, ldt, B, E, p_real, n_r, p_fake, n_f = _critic_args("critic_loss_grad", e, t, p_real, p_fake)
+    _dev(ws, *d)
+    if ws.numel() * ws.element_size() < 12 * B:
+        raise ValueError(f"critic_loss_grad: ws holds {ws.numel()} floats, B = {B} rows need {3 * B}")
+    for g in d:
+        if g is not None and (g.dtype != torch.float32 or g.numel() != 1):
+            raise TypeError("critic_loss_grad: the upstream gradients are one-element fp32 tensors or None")
+    de = torch.empty(B, E, device=e.device) if need[0] else None
+    dr = torch.empty_like(p_real) if need[1] else None
+    df = torch.empty_like(p_fake) if need[2] else None
+    L.call("avc_critic_loss_grad", e.data_ptr(), lde, t.data_ptr(), ldt, B, E, p_real.data_ptr(), n_r,
+           p_fake.data_ptr(), n_f, float(lambda_cls), float(lambda_dis), ws.data_ptr(), *[_ptr(g) for g in d],
+           _ptr(de), E, _ptr(dr), _ptr(df), stream())
+    return de, dr, df
