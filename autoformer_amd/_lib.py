@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # AVC_LIB_PATH: another build of the same ABI (same-box A/B timing of two builds, tools/ only)
 LIB_PATH = os.environ.get("AVC_LIB_PATH") or os.path.join(HERE, "libautovc_hip.so")
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip", "ragged.hip", "melgan_ragged.hip", "ge2e.hip", "xent.hip", "critic_loss.hip"]
+SOURCES = ["gemm_ring.hip", "conv_ring.hip", "gemm_conv.hip", "gemm_nt.hip", "gemm_tt.hip", "gemm.hip", "bn.hip", "lstm.hip", "lstm_small.hip", "lstm_persist.hip", "lstm_infer.hip", "lstm2.hip", "elem.hip", "norm.hip", "variants.hip", "melgan.hip", "fold.hip", "disc.hip", "events.hip", "metadv.hip", "audio.hip", "resample.hip", "bn_seg.hip", "seg_moments.hip", "ragged.hip", "melgan_ragged.hip", "ge2e.hip", "xent.hip", "critic_loss.hip", "cycle_loss.hip"]
 ABI_VERSION = 31
 
 F32, BF16 = 0, 1
@@ -307,6 +307,18 @@ _SIGS_CRITIC = {
                                      c_int, c_void_p, c_void_p, c_void_p]),
 }
 
+# The cycle step's loss tail of include/autovc_hip_cycle.h: a twelfth header and a twelfth table, added the same
+# way (no ABI bump; the first eleven tables are as they were); lib() binds all twelve.
+CYCLE_MAX_NX, CYCLE_GRID = 2 ** 31 - 1, 256
+_CYCLE_IN = [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+             c_int, c_void_p, c_void_p, c_ll]
+_SIGS_CYCLE = {
+    "avc_cycle_loss_ws": (c_size, [c_int, c_ll]),
+    "avc_cycle_loss": (c_int, _CYCLE_IN + [c_void_p, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "avc_cycle_loss_grad": (c_int, _CYCLE_IN + [c_float, c_float, c_float, c_void_p] + [c_void_p] * 6
+                            + [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -326,7 +338,8 @@ def build(verbose: bool = False, force: bool = False) -> str:
                                                                         "autovc_hip_ragged.h",
                                                                         "autovc_hip_vocoder.h",
                                                                         "autovc_hip_ge2e.h", "autovc_hip_xent.h",
-                                                                        "autovc_hip_critic.h")]
+                                                                        "autovc_hip_critic.h",
+                                                                        "autovc_hip_cycle.h")]
         newest = max(os.path.getmtime(p) for p in deps)
         if os.path.getmtime(LIB_PATH) >= newest:
             return LIB_PATH
@@ -366,7 +379,7 @@ def lib():
                                   + list(_SIGS_RESAMPLE.items()) + list(_SIGS_EVAL.items()) + list(_SIGS_SEG.items())
                                   + list(_SIGS_RAGGED.items()) + list(_SIGS_VOCODER.items())
                                   + list(_SIGS_GE2E.items()) + list(_SIGS_XENT.items())
-                                  + list(_SIGS_CRITIC.items())):
+                                  + list(_SIGS_CRITIC.items()) + list(_SIGS_CYCLE.items())):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -452,3 +465,8 @@ def exported_symbols_xent():
 def exported_symbols_critic():
     """The entry points of include/autovc_hip_critic.h (the critic step's fused loss tail and its gradients)."""
     return list(_SIGS_CRITIC.keys())
+
+
+def exported_symbols_cycle():
+    """The entry points of include/autovc_hip_cycle.h (the cycle step's fused loss tail and its gradients)."""
+    return list(_SIGS_CYCLE.keys())

@@ -16,27 +16,11 @@
 // probabilities i, i + 256, ...; a butterfly per wave, then the four waves' partials through LDS, added in
 // wave order by thread 0.  Backward: one workgroup per row of de, then one per 256 probabilities; elementwise.
 // The launch is latency, not arithmetic: the training shape is B <= 64, E = 256, n = B.
-#include <math.h>
-
 #include "../../include/autovc_hip_critic.h"
-#include "common.h"
+#include "critic_internal.h"
 
 namespace {
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
-constexpr float COS_EPS = 1e-12f;  // ATen's EPSILON of cosine_embedding_loss, and of BCE's backward
-constexpr float LOG_FLOOR = -100.f;  // nn.BCELoss clamps its logarithms here
-
-// columns 4u .. 4u + 3 of a row of E floats; the scalar form leaves what lies past E at zero (never added)
-template <bool VEC>
-__device__ __forceinline__ f32x4 load_group(const float* __restrict__ row, int u, int E) {
-  if (VEC) return *reinterpret_cast<const f32x4*>(row + 4 * u);
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (4 * u + k < E) v[k] = row[4 * u + k];
-  return v;
-}
+using namespace critic;  // the rows, the sums and their gradients: shared with cycle_loss.hip, one order for both
 
 template <bool VEC>
 __global__ void __launch_bounds__(THREADS)
@@ -46,39 +30,8 @@ __global__ void __launch_bounds__(THREADS)
                        float* __restrict__ ws) {
   __shared__ float red[3][WAVES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int U = (E + 3) >> 2;
-
-  float cpart = 0.f;  // the wave's sum of 1 - cos over its rows, in row order
-  for (int b = wave; b < B; b += WAVES) {
-    const float* er = e + (size_t)b * lde;
-    const float* tr = t + (size_t)b * ldt;
-    float dot = 0.f, se = 0.f, st = 0.f;
-    for (int u = lane; u < U; u += 64) {
-      const f32x4 ev = load_group<VEC>(er, u, E), tv = load_group<VEC>(tr, u, E);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (VEC || 4 * u + k < E) {
-          dot = fmaf(ev[k], tv[k], dot);
-          se = fmaf(ev[k], ev[k], se);
-          st = fmaf(tv[k], tv[k], st);
-        }
-      }
-    }
-    dot = warp_sum(dot);
-    const float m1 = warp_sum(se) + COS_EPS, m2 = warp_sum(st) + COS_EPS;
-    if (lane == 0) {
-      ws[3 * b + 0] = dot;
-      ws[3 * b + 1] = m1;
-      ws[3 * b + 2] = m2;
-    }
-    cpart += 1.f - dot / sqrtf(m1 * m2);
-  }
-
-  float rpart = 0.f, fpart = 0.f;
-  for (int i = tid; i < n_r; i += THREADS) rpart -= fmaxf(logf(p_real[i]), LOG_FLOOR);
-  for (int i = tid; i < n_f; i += THREADS) fpart -= fmaxf(log1pf(-p_fake[i]), LOG_FLOOR);
-  rpart = warp_sum(rpart);
-  fpart = warp_sum(fpart);
+  const float cpart = cos_rows<VEC>(e, lde, t, ldt, B, E, ws, lane, wave);
+  const float rpart = real_sum(p_real, n_r, tid), fpart = fake_sum(p_fake, n_f, tid);
   if (lane == 0) {
     red[0][wave] = cpart;
     red[1][wave] = rpart;
@@ -86,9 +39,9 @@ __global__ void __launch_bounds__(THREADS)
   }
   __syncthreads();
   if (tid == 0) {
-    const float c = (((red[0][0] + red[0][1]) + red[0][2]) + red[0][3]) / (float)B;
-    const float r = (((red[1][0] + red[1][1]) + red[1][2]) + red[1][3]) / (float)n_r;
-    const float f = (((red[2][0] + red[2][1]) + red[2][2]) + red[2][3]) / (float)n_f;
+    const float c = sum4(red[0]) / (float)B;
+    const float r = sum4(red[1]) / (float)n_r;
+    const float f = sum4(red[2]) / (float)n_f;
     const float d = r + f;
     const float extra = fmaf(lambda_dis, d, lambda_cls * c);
     out[0] = c;
@@ -111,42 +64,19 @@ __global__ void __launch_bounds__(THREADS)
   int blk = blockIdx.x;
   const float g_sum = (g_extra ? g_extra[0] : 0.f) + (g_total ? g_total[0] : 0.f);
   if (blk < row_blocks) {  // row blk of de
-    const int b = blk;
     const float g_c = fmaf(lambda_cls, g_sum, g_closs ? g_closs[0] : 0.f);
-    const float dot = ws[3 * b + 0], m1 = ws[3 * b + 1], m2 = ws[3 * b + 2];
-    const float denom = sqrtf(m1 * m2), s = -(g_c / (float)B);
-    const float ct = s / denom, ce = s * (dot / denom) / m1;
-    const float* er = e + (size_t)b * lde;
-    const float* tr = t + (size_t)b * ldt;
-    float* dr = de + (size_t)b * ldde;
-    const int U = (E + 3) >> 2;
-    for (int u = tid; u < U; u += THREADS) {
-      const f32x4 ev = load_group<VEC>(er, u, E), tv = load_group<VEC>(tr, u, E);
-      f32x4 g;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) g[k] = fmaf(ct, tv[k], -(ce * ev[k]));
-      if (VEC) {
-        *reinterpret_cast<f32x4*>(dr + 4 * u) = g;
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (4 * u + k < E) dr[4 * u + k] = g[k];
-      }
-    }
+    de_row<VEC>(e, lde, t, ldt, B, E, ws, g_c, de, ldde, blk, tid);
     return;
   }
   blk -= row_blocks;
   const float g_d = fmaf(lambda_dis, g_sum, g_dloss ? g_dloss[0] : 0.f);
   const bool real = blk < real_blocks;
   if (!real) blk -= real_blocks;
-  const float* p = real ? p_real : p_fake;
-  float* dp = real ? dp_real : dp_fake;
-  const int n = real ? n_r : n_f;
   const int i = blk * THREADS + tid;
-  if (i < n) {
-    const float v = p[i], y = real ? 1.f : 0.f;
-    dp[i] = g_d * (v - y) / fmaxf(v * (1.f - v), COS_EPS) / (float)n;
-  }
+  if (real)
+    dp_elem(p_real, dp_real, n_r, i, 1.f, g_d);
+  else
+    dp_elem(p_fake, dp_fake, n_f, i, 0.f, g_d);
 }
 
 bool b_ok(int B) { return B >= 1 && B <= AVC_CRITIC_MAX_B; }

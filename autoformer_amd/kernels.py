@@ -1610,3 +1610,70 @@ def critic_loss_grad(e, t, p_real, p_fake, lambda_cls, lambda_dis, ws, d, need):
            p_fake.data_ptr(), n_f, float(lambda_cls), float(lambda_dis), ws.data_ptr(), *[_ptr(g) for g in d],
            _ptr(de), E, _ptr(dr), _ptr(df), stream())
     return de, dr, df
+
+
+# ------------------------------------------------------------------------- cycle loss tail (autovc_hip_cycle.h)
+def _cycle_args(who, e1, t1, e2, t2, p_real, p_fake, x, y):
+    """The checked leading arguments of the cycle loss calls: the four row operands with their strides, B, E, the
+    probabilities with their counts, x, y, n_x."""
+    a = _critic_args(who, e1, t1, p_real, p_fake)
+    b = _critic_args(who, e2, t2, p_real, p_fake)
+    if e1.shape != e2.shape:
+        raise ValueError(f"{who}: both pairs must have one shape, got {tuple(e1.shape)} and {tuple(e2.shape)}")
+    _dev(x, y)
+    for name, v in (("x", x), ("y", y)):
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or not v.is_contiguous():
+            raise TypeError(f"{who}: {name} must be a contiguous fp32 tensor")
+    n_x = x.numel()
+    if y.numel() != n_x or not 1 <= n_x <= L.CYCLE_MAX_NX:
+        raise ValueError(f"{who}: x and y must hold the same 1 <= n_x <= {L.CYCLE_MAX_NX} elements, got {n_x} and "
+                         f"{y.numel()}")
+    lde1, ldt1, lde2, ldt2, B, E, n_r, n_f = a[1], a[3], b[1], b[3], a[4], a[5], a[7], a[9]
+    ptrs = (e1.data_ptr(), lde1, t1.data_ptr(), ldt1, e2.data_ptr(), lde2, t2.data_ptr(), ldt2, B, E, p_real.data_ptr(),
+            n_r, p_fake.data_ptr(), n_f, x.data_ptr(), y.data_ptr(), n_x)
+    return ptrs, B, E, n_x
+
+
+def cycle_loss(e1, t1, e2, t2, p_real, p_fake, x, y, lambda_cls, lambda_dis, lambda_cycle, base=None):
+    """The cycle step's loss tail in one launch (avc_cycle_loss): (out, ws) with out a (6,) device tensor
+    [c_trans, c_reconst, d_loss, cycle, extra, base + extra] -- c_trans = F.cosine_embedding_loss(e1, t1, ones),
+    c_reconst the same of (e2, t2), d_loss = BCE(p_real, 1) + BCE(p_fake, 0), cycle = F.mse_loss(x, y), extra =
+    lambda_cls (c_trans + c_reconst) + lambda_dis d_loss + lambda_cycle cycle -- and ws what cycle_loss_grad reads.
+    Rows: fp32 (B, E) with unit column stride; x, y: contiguous fp32 of one size; base: a one-element fp32 device
+    tensor or None.  Deterministic."""
+    ptrs, B, _, n_x = _cycle_args("cycle_loss", e1, t1, e2, t2, p_real, p_fake, x, y)
+    if base is not None:
+        _dev(base)
+        if base.dtype != torch.float32 or base.numel() != 1:
+            raise TypeError(f"cycle_loss: base must be a one-element fp32 tensor, got {base.dtype} {tuple(base.shape)}")
+    dev = e1.device
+    out = torch.empty(6, device=dev)
+    ws = torch.empty(int(L.lib().avc_cycle_loss_ws(B, n_x)) // 4, device=dev)
+    L.call("avc_cycle_loss", *ptrs, _ptr(base), float(lambda_cls), float(lambda_dis), float(lambda_cycle),
+           out.data_ptr(), ws.data_ptr(), stream())
+    return out, ws
+
+
+def cycle_loss_grad(e1, t1, e2, t2, p_real, p_fake, x, y, lambda_cls, lambda_dis, lambda_cycle, ws, d, need):
+    """Gradients of cycle_loss's outputs in one launch (avc_cycle_loss_grad): d = the 6 upstream device scalars of
+    out[0..5] (or None), need = (e1, e2, p_real, p_fake, y) flags; returns the five gradients (None where not
+    needed)."""
+    ptrs, B, E, n_x = _cycle_args("cycle_loss_grad", e1, t1, e2, t2, p_real, p_fake, x, y)
+    _dev(ws, *d)
+    want = int(L.lib().avc_cycle_loss_ws(B, n_x))
+    if ws.numel() * ws.element_size() < want:
+        raise ValueError(f"cycle_loss_grad: ws holds {ws.numel() * ws.element_size()} bytes, B = {B} needs {want}")
+    if len(d) != 6:
+        raise ValueError("cycle_loss_grad: six upstream gradients (or None), one per output")
+    for g in d:
+        if g is not None and (g.dtype != torch.float32 or g.numel() != 1):
+            raise TypeError("cycle_loss_grad: the upstream gradients are one-element fp32 tensors or None")
+    dev = e1.device
+    de1 = torch.empty(B, E, device=dev) if need[0] else None
+    de2 = torch.empty(B, E, device=dev) if need[1] else None
+    dr = torch.empty_like(p_real) if need[2] else None
+    df = torch.empty_like(p_fake) if need[3] else None
+    dy = torch.empty_like(y) if need[4] else None
+    L.call("avc_cycle_loss_grad", *ptrs, float(lambda_cls), float(lambda_dis), float(lambda_cycle), ws.data_ptr(),
+           *[_ptr(g) for g in d], _ptr(de1), E, _ptr(de2), E, _ptr(dr), _ptr(df), _ptr(dy), stream())
+    return de1, de2, dr, df, dy

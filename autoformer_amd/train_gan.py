@@ -219,9 +219,20 @@ class GanVer1Solver(Solver):
         self.D = Discriminator()
         for m in (self.VC, self.C, self.D):
             m.to(self.device)
-        self.step = CriticStep(self.VC, self.C, self.D, 0.0001, self.lambda_cd, self.lambda_cls, self.lambda_dis,
-                               self.use_adain)
+        self.step = self.make_step()
         self.vc_optimizer, self.c_optimizer, self.d_optimizer = self.step.vc_opt, self.step.c_opt, self.step.d_opt
+
+    def make_step(self):
+        """The step object over the three modules (a subclass with another kind of iteration overrides it)."""
+        return CriticStep(self.VC, self.C, self.D, 0.0001, self.lambda_cd, self.lambda_cls, self.lambda_dis,
+                          self.use_adain)
+
+    def critic_iteration(self, x_source, org_style):
+        """A critic iteration: draws the second batch and C's window starts; returns the VC loss's three parts
+        followed by the critic-only values, in log_keys' order."""
+        x_target, target_style = self.get_data()
+        lefts = self.C.draw_lefts(x_source.shape[-2])
+        return self.step.critic_step(x_source, org_style, x_target, target_style, lefts)
 
     def reset_grad(self):
         self.vc_optimizer.zero_grad()
@@ -247,23 +258,22 @@ class GanVer1Solver(Solver):
         print(log)
 
     def train(self):
-        """The loop; returns the five logged values of every iteration (read from the device once, at the end)."""
+        """The loop; returns the logged values of every iteration (read from the device once, at the end)."""
         print("Start training...")
         start_time = time.time()
         self._data_iter = None
         zero = torch.zeros((), device=self.device)
-        last_c, last_d = zero, zero
+        last = [zero] * (len(self.log_keys) - 3)
         rows = []
         for i in range(self.num_iters):
             x_source, org_style = self.get_data()
             self.VC, self.C, self.D = self.VC.train(), self.C.train(), self.D.train()
             if critic_due(i, self.n_critic, self.pretrained_step):
-                x_target, target_style = self.get_data()
-                lefts = self.C.draw_lefts(x_source.shape[-2])
-                *parts, last_c, last_d = self.step.critic_step(x_source, org_style, x_target, target_style, lefts)
+                out = self.critic_iteration(x_source, org_style)
+                parts, last = out[:3], list(out[3:])
             else:
                 parts = self.step.vc_step(x_source, org_style)
-            rows.append(torch.stack([*parts, last_c, last_d]))
+            rows.append(torch.stack([*parts, *last]))
             if (i + 1) % self.log_step == 0:
                 loss = dict(zip(self.log_keys, rows[-1].tolist()))
                 K.check_faults(zero.device)
@@ -333,7 +343,12 @@ def config_from_args(args):
 def main(argv=None):
     """Parse, build GanVer1Solver and train; returns the per-iteration losses."""
     args = build_parser().parse_args(argv)
-    config = config_from_args(args)
+    return run(args, config_from_args(args), GanVer1Solver)
+
+
+def run(args, config, solver_cls, more_labels=()):
+    """Train solver_cls on the parsed flags and save the three modules; more_labels: (label, value) pairs added to
+    the printed configuration after the lambdas."""
     if not str(args.device).startswith("cuda"):
         raise SystemExit(f"--device {args.device}: the HIP kernels need a GPU")
     if not torch.cuda.is_available():
@@ -343,8 +358,8 @@ def main(argv=None):
     A.set_compute(args.dtype)
     print(" --- Use Config  ---")
     for label, v in (("Lambda cd", config.lambda_cd), ("Lambda cls", config.lambda_cls),
-                     ("Lambda dis", config.lambda_dis), ("N critic", config.n_critic), ("Use Adain", config.use_adain),
-                     ("VC Pretrained step", config.pretrained_step)):
+                     ("Lambda dis", config.lambda_dis), *more_labels, ("N critic", config.n_critic),
+                     ("Use Adain", config.use_adain), ("VC Pretrained step", config.pretrained_step)):
         print(f" {label} --- {v}")
     print(" ----------------------")
     if args.synthetic:
@@ -354,7 +369,7 @@ def main(argv=None):
 
         loader = get_loader(args.data_dir, dim_neck=config.dim_neck, batch_size=args.batch_size,
                             len_crop=args.len_crop)
-    solver = GanVer1Solver(loader, config)
+    solver = solver_cls(loader, config)
     if args.det_init:
         from .detinit import det_init_
 
